@@ -7,7 +7,7 @@ is one complete breadth-first model-checking run of that model on the GPU
 (seen-set re-zeroed, every level expanded; the state store stays allocated
 between steps, the inputs are the spec/cfg only).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 N > 1 (torchrun, one process per GPU): the model is checked ONCE by all
 ranks together: fingerprints are owner-partitioned and every level chunk
@@ -15,8 +15,25 @@ exchanges candidates, acknowledgements and new states with three RCCL
 all-to-alls (raft-tla_amd/shard.py); value = the model's distinct states /
 max-over-ranks time of one run, "scaling": "strong" (total work fixed).
 
-Beside the headline, every invocation measures (same N, same path, outside the headline's timed
-region; each with its own barrier-bracketed max-over-ranks timing):
+A plain run sets up, does W untimed and K timed steps and prints the JSON line: the headline, the
+roofline of the dominant kernel and the dedup-set GB/s, all from the timed steps' own HIP events.
+
+--dump-outputs DIR writes what the last timed step returned to its caller (raftmc.Result) as float64
+arrays, identical from run to run for the same arguments (the inputs are the spec/cfg and the fixed
+fingerprint seed):
+  DIR/summary.npy           [verdict code (raftmc.VERDICTS), generated, distinct, depth, left_on_queue,
+                            generated_in_model]
+  DIR/level_states.npy      distinct states per BFS level
+  DIR/action_generated.npy  generated states per action, the actions in name order (the line's
+                            "outputs"."actions")
+  DIR/action_distinct.npy   distinct states per action, only with --workers 1: under -workers N the
+                            action credited with a state is first-come, as in TLC
+
+--full adds the measurements below, each in runs of its own (same N, same path, outside the headline's
+timed region; each with its own barrier-bracketed max-over-ranks timing); --no-extra,
+--no-cpu-baseline and --fifo-steps 0 leave single ones out of a --full run:
+  tlc_workers_1   C2 in TLC's single-worker FIFO order (N = 1)
+  dedup_set       its seen-set probe figures (an extra run of the instrumented dedup kernel, N = 1)
   scale_workload  C5v2 to depth 12 (configs/c5v2.cfg: BASELINE configs[4]'s 5-server model,
                   482M distinct states), the workload large enough for a 1/2/4/8-GPU curve
   scale_workload_configs4  C5v2 to depth 13 (2.44e9 distinct, its last level counted, not stored:
@@ -40,10 +57,10 @@ The JSON line adds:
                 figures only when the summary names the same kernel AND workload; pipeline_frac =
                 the same bytes over the whole step time (every kernel and the host between them)
   dedup_set     the BASELINE metric's second half: dedup-set GB/s (G_in*8 + D*16) / (merge +
-                probe kernel time), seen-set probes/s (the device's probe count / that time:
-                successors the same workgroup produced twice probe once) and the transaction-level
-                figure (probes * 64 B / that time, against the 8 TB/s peak)
-  cpu_baseline  the builder's multithreaded C++ CPU BFS (oracle/cpu_bfs.cpp: TLC-style workers, a
+                probe kernel time); with --full also seen-set probes/s (the device's probe count /
+                that time: successors the same workgroup produced twice probe once) and the
+                transaction-level figure (probes * 64 B / that time, against the 8 TB/s peak)
+  cpu_baseline  (--full) the builder's multithreaded C++ CPU BFS (oracle/cpu_bfs.cpp: TLC-style workers, a
                 lock-free fingerprint set, the product's packed successor function and invariants;
                 "port") with threads = the host cores of this job, on the whole C2 (bounded by
                 --cpu-states); beside it the value-model oracle (oracle/main.cpp, one thread) on a
@@ -102,6 +119,24 @@ def workload_name(cfg, max_depth):
     return name + (" to depth %d" % max_depth if max_depth else "")
 
 
+def dump_outputs(dirname, res, verdicts, fifo_order):
+    """--dump-outputs: the counts raftmc.Result hands a caller of run(), as float64 arrays (every count
+    is far below 2^53).  Only what does not depend on the order in which a level's states are found:
+    the per-action distinct counts are written in TLC's FIFO order (fifo_order) alone."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    code = {v: k for k, v in verdicts.items()}[res.verdict]
+    names = sorted(res.actions)
+    arrays = {"summary": [code, res.generated, res.distinct, res.depth, res.left_on_queue, res.generated_in_model],
+              "level_states": [lv[0] for lv in res.levels],
+              "action_generated": [res.actions[k][0] for k in names]}
+    if fifo_order:
+        arrays["action_distinct"] = [res.actions[k][1] for k in names]
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.asarray(a, dtype=np.float64))
+    return {"dir": dirname, "arrays": {k: len(v) for k, v in arrays.items()}, "dtype": "float64", "actions": names}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -126,7 +161,12 @@ def main():
     ap.add_argument("--traffic-json", default=None)
     ap.add_argument("--valu-json", default=None)
     ap.add_argument("--no-extra", action="store_true", help="skip the scale_workload / variants measurements")
+    ap.add_argument("--full", action="store_true", help="also the FIFO run, the probe count, the scale workloads and "
+                                                        "variants, and the CPU baselines (runs of their own)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's result as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps needs at least 1 timed step, --warmup at least 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -186,10 +226,13 @@ def main():
 
     res, per_step = measure(args.config, args.max_depth, args.steps, args.warmup, args.state_store_bytes,
                             args.fp_table_bytes, args.workers)
+    outputs = None
+    if args.dump_outputs and rank == 0:   # the sharded result is global: every rank holds the same counts
+        outputs = dump_outputs(args.dump_outputs, res, mod.raftmc.VERDICTS, args.workers == 1)
     # the seen-set probes of one run, counted by the instrumented dedup kernel in a run of its own
     # (RAFTMC_COUNT_PROBES; the timed runs use the uninstrumented one)
     probes_per_run = None
-    if world == 1 and args.workers != 1:
+    if args.full and world == 1 and args.workers != 1:
         os.environ["RAFTMC_COUNT_PROBES"] = "1"
         try:
             with checker(args.config, args.max_depth, args.state_store_bytes, args.fp_table_bytes, args.workers) as mc:
@@ -198,7 +241,7 @@ def main():
             del os.environ["RAFTMC_COUNT_PROBES"]
     # TLC -workers 1 (FIFO order) on the same model, outside the timed region: its cost is reported
     fifo = None
-    if world == 1 and args.workers != 1 and args.fifo_steps > 0:
+    if args.full and world == 1 and args.workers != 1 and args.fifo_steps > 0:
         r1, t1 = measure(args.config, args.max_depth, args.fifo_steps, 1, args.state_store_bytes, args.fp_table_bytes, 1)
         fifo = {"ms_per_step": t1 * 1e3, "steps": args.fifo_steps, "distinct_per_run": r1.distinct,
                 "generated_per_run": r1.generated, "kernels_ms": {k: v["ms"] for k, v in r1.kernels.items() if v["launches"]}}
@@ -259,7 +302,7 @@ def main():
             return {"workload": "C2 via the generated path", "error": str(e)[:300]}
 
     extra = {}
-    if not args.no_extra:
+    if args.full and not args.no_extra:
         # C5v2 to depth 12: 482M states of 160 B + 8 B parent pointers = 81 GB, and the host spill's
         # 1.5x margin on the next level must not trigger: 128 GiB at N=1 (a 96 GiB store spilled the
         # completed levels to host memory every run, 1.04 s instead of 0.23 s)
@@ -352,22 +395,27 @@ def main():
             # probes: the device's count of fingerprints that reached the seen-set (a successor that the
             # same 256 parents produced before is filtered in LDS and never probes); the transaction-level
             # figure prices each probe at one 64-B HBM line (8 TB/s / 64 B = 125 G/s)
-            probes = probes_per_run or 0
             line["dedup_set"] = {"GBps": (res.generated_in_model * 8 + res.distinct * 16) / ded_s / 1e9,
-                                 "probes_per_s": probes / ded_s, "probes_per_run": probes,
-                                 "successors_per_s": res.generated_in_model / ded_s,
-                                 "transaction_GBps": probes * 64 / ded_s / 1e9,
-                                 "transaction_frac": probes * 64 / ded_s / 1e9 / HBM_PEAK_GBS, "ms": ded_s * 1e3,
-                                 "bytes": "G_in*8 + D*16 (SURVEY.md 8(d) dedup-set metric) / (merge + probe kernel time); "
-                                          "transaction: probes * 64 B / the same time; probes_per_run counted in an extra "
-                                          "run by the instrumented dedup kernel (RAFTMC_COUNT_PROBES), rates over the timed runs' time"}
+                                 "successors_per_s": res.generated_in_model / ded_s, "ms": ded_s * 1e3,
+                                 "bytes": "G_in*8 + D*16 (SURVEY.md 8(d) dedup-set metric) / (merge + probe kernel time)"}
+            if args.full:   # the probe figures need the extra run above
+                probes = probes_per_run or 0
+                line["dedup_set"].update({
+                    "probes_per_s": probes / ded_s, "probes_per_run": probes,
+                    "transaction_GBps": probes * 64 / ded_s / 1e9,
+                    "transaction_frac": probes * 64 / ded_s / 1e9 / HBM_PEAK_GBS,
+                    "bytes": "G_in*8 + D*16 (SURVEY.md 8(d) dedup-set metric) / (merge + probe kernel time); "
+                             "transaction: probes * 64 B / the same time; probes_per_run counted in an extra "
+                             "run by the instrumented dedup kernel (RAFTMC_COUNT_PROBES), rates over the timed runs' time"})
         # VALU issue fraction of the dominant kernel: PMC instruction count per launch from profiles/, live
         # launch time; MI355X_MICROARCH.md: 4 SIMD-32 per CU, a wave64 VALU instruction issues in 2 cycles
         vj = pmc_summary(args.valu_json, defaults[1])
         if vj:
             line["roofline"]["valu_issue_frac"] = vj["valu_insts_per_launch"] / (avg_s * 256 * 2 * 2.4e9)
         line.update(extra)
-        if not args.no_cpu_baseline and os.path.basename(args.config) == "c2.cfg" and not args.max_depth:
+        if outputs is not None:
+            line["outputs"] = outputs
+        if args.full and not args.no_cpu_baseline and os.path.basename(args.config) == "c2.cfg" and not args.max_depth:
             line["cpu_baseline"] = cpu_baseline(args.config, args.cpu_states, args.cpu_workers, args.oracle_states)
         print(json.dumps(line), flush=True)
     if dist is not None:

@@ -5,7 +5,7 @@
 # (after a GPU fault, abort, timeout or hang nothing else touches the GPU in that call).
 #   tests[=EXPR]        pytest -m gpu -x (optionally -k EXPR); testsall[=EXPR]: without -x
 #   smoke               __graft_entry__.smoke()
-#   bench               bench.py with its defaults (the driver's line)
+#   bench               bench.py --full (the headline and every measurement beside it)
 #   c2[=NAME[=LIB]]     bench.py C2 only (no extras, no CPU baseline) with library LIB (default: the
 #                       in-tree build), 8 timed steps; prints ms/step, kernels, seen-set probes
 #   c2f[=NAME[=LIB]]    the C2 line and the FIFO (-workers 1) run beside it
@@ -34,11 +34,11 @@ for step in "$@"; do
       timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > "$O/smoke.log" 2>&1
       rc=$?; tail -1 "$O/smoke.log" ;;
     bench)
-      timeout -k 10 600 python -u bench.py > "$O/bench.json" 2> "$O/bench.err"
+      timeout -k 10 600 python -u bench.py --full > "$O/bench.json" 2> "$O/bench.err"
       rc=$?; cut -c1-600 "$O/bench.json" ;;
     c2)
       n=${arg%%=*}; lib=${arg#*=}; [ "$lib" = "$arg" ] && lib=""; n=${n:-base}
-      timeout -k 10 200 env ${lib:+RAFTMC_LIB=$lib} python3 bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-extra --fifo-steps 0 \
+      timeout -k 10 200 env ${lib:+RAFTMC_LIB=$lib} python3 bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --no-extra --fifo-steps 0 \
         > "$O/c2_$n.json" 2> "$O/c2_$n.err"
       rc=$?
       [ $rc -eq 0 ] && python3 -c "
@@ -48,7 +48,7 @@ print('$n', round(d['ms_per_step'], 2), {k: round(v['ms'], 2) for k, v in d['ker
       'probes', d.get('dedup_set', {}).get('probes_per_run'))" ;;
     c2f)   # c2f[=NAME[=LIB]]: the C2 line and TLC -workers 1 (FIFO order) beside it
       n=${arg%%=*}; lib=${arg#*=}; [ "$lib" = "$arg" ] && lib=""; n=${n:-base}
-      timeout -k 10 300 env ${lib:+RAFTMC_LIB=$lib} python3 bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-extra --fifo-steps 3 \
+      timeout -k 10 300 env ${lib:+RAFTMC_LIB=$lib} python3 bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-extra --fifo-steps 3 \
         > "$O/c2f_$n.json" 2> "$O/c2f_$n.err"
       rc=$?
       [ $rc -eq 0 ] && python3 -c "
@@ -57,7 +57,7 @@ d = json.loads(open('$O/c2f_$n.json').read().strip().splitlines()[-1])
 f = d['tlc_workers_1']
 print('$n', round(d['ms_per_step'], 2), 'fifo', round(f['ms_per_step'], 2), {k: round(v, 2) for k, v in f['kernels_ms'].items()})" ;;
     c2t)
-      timeout -k 10 200 python3 bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-extra --fifo-steps 0 \
+      timeout -k 10 200 python3 bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --no-extra --fifo-steps 0 \
         --fp-table-bytes $((arg << 30)) > "$O/c2t_$arg.json" 2> "$O/c2t_$arg.err"
       rc=$?
       [ $rc -eq 0 ] && python3 -c "

@@ -13,6 +13,14 @@ ORIG_MC = os.path.join(CONFIGS, "raft_original_mc.tla")
 MEMB_MC = os.path.join(CONFIGS, "raft_membership_mc.tla")
 
 
+def native_build_dir():
+    """Where the tests compile their host harnesses (tests/native/*.cpp): inside this checkout, so a
+    binary is never shared with another checkout or another user's run."""
+    d = os.path.join(ROOT, "tests", "native", "_build")
+    os.makedirs(d, exist_ok=True)
+    return d
+
+
 def build_oracle():
     subprocess.run(["make", "-s", "-C", ORACLE_DIR], check=True)
     return ORACLE_BIN

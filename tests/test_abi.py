@@ -322,18 +322,19 @@ def test_prefix_taken_from_extended_module(raftmc, tmp_path):
         assert mc.describe()["history_prefixes"] == {"MajorityOfClusterRestarts_constraint": 28}
 
 
-def test_checkpoint_api_scope(raftmc):
+def test_checkpoint_api_scope(raftmc, tmp_path):
     """Checkpoints exist for both spec families (TLC -checkpoint / -recover); a negative
     interval is refused."""
     lib = raftmc.load_library()
+    ckpt = str(tmp_path / "x.ckpt")
     with raftmc.ModelChecker(MEMB_MC, os.path.join(CONFIGS, "membership_shipped.cfg")) as mc:
-        assert lib.mc_set_checkpoint(mc.h, b"/tmp/x.ckpt", 1) == 0
-        assert lib.mc_set_checkpoint(mc.h, b"/tmp/x.ckpt", -1) == -1
-        assert lib.mc_set_recover(mc.h, b"/tmp/x.ckpt") == 0
+        assert lib.mc_set_checkpoint(mc.h, ckpt.encode(), 1) == 0
+        assert lib.mc_set_checkpoint(mc.h, ckpt.encode(), -1) == -1
+        assert lib.mc_set_recover(mc.h, ckpt.encode()) == 0
         mc.set_recover(None)
     with raftmc.ModelChecker(ORIG_MC, os.path.join(CONFIGS, "c1.cfg")) as mc:
-        assert lib.mc_set_checkpoint(mc.h, b"/tmp/x.ckpt", -1) == -1
-        mc.set_checkpoint("/tmp/x.ckpt", 2)
+        assert lib.mc_set_checkpoint(mc.h, ckpt.encode(), -1) == -1
+        mc.set_checkpoint(ckpt, 2)
         mc.set_checkpoint(None)
         mc.set_recover(None)
 

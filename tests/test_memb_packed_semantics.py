@@ -13,7 +13,7 @@ import tempfile
 
 import pytest
 
-from oracle_util import CONFIGS, GOLDEN, ROOT, golden_file
+from oracle_util import CONFIGS, GOLDEN, ROOT, golden_file, native_build_dir
 
 SHAPES = {"membership_shipped": (3, 2), "memb_dynamic3": (3, 2), "memb_nosym": (3, 2), "memb_two": (2, 1),
           "memb_four": (4, 2), "memb_four_scale": (4, 2), "memb_async": (3, 2), "scen_CommitWhenConcurrentLeaders_punct": (3, 2),
@@ -22,7 +22,7 @@ FIX = json.load(open(os.path.join(GOLDEN, "memb_parity.json")))
 
 
 def build_harness(shape):
-    out = os.path.join(tempfile.gettempdir(), "memb_host_bfs_%d%d" % shape)
+    out = os.path.join(native_build_dir(), "memb_host_bfs_%d%d" % shape)
     csrc = os.path.join(ROOT, "raft-tla_amd", "csrc")
     src = [os.path.join(ROOT, "tests", "native", "memb_host_bfs.cpp"), os.path.join(csrc, "model.cpp"),
            os.path.join(csrc, "memb_model.cpp"), os.path.join(csrc, "tla_value.cpp")]

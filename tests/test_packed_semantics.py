@@ -11,14 +11,14 @@ import tempfile
 
 import pytest
 
-from oracle_util import CONFIGS, GOLDEN, ROOT
+from oracle_util import CONFIGS, GOLDEN, ROOT, native_build_dir
 
 SHAPES = {"c1": (3, 1, 2, 1, 2), "parity_single": (1, 2, 3, 2, 3), "parity_pair": (2, 1, 2, 1, 5),
           "parity_pair_neg": (2, 1, 2, 1, 5), "parity_trio": (3, 2, 3, 2, 2), "parity_pair6": (2, 1, 2, 1, 6)}
 
 
 def build_harness(shape):
-    out = os.path.join(tempfile.gettempdir(), "orig_host_bfs_%d%d%d%d%d" % shape)
+    out = os.path.join(native_build_dir(), "orig_host_bfs_%d%d%d%d%d" % shape)
     src = [os.path.join(ROOT, "tests", "native", "orig_host_bfs.cpp"),
            os.path.join(ROOT, "raft-tla_amd", "csrc", "model.cpp"),
            os.path.join(ROOT, "raft-tla_amd", "csrc", "orig_model.cpp")]
@@ -97,7 +97,7 @@ def test_compact_election_records_replayed_by_oracle():
     text (records decoded from the compact form) through the literal restatement."""
     from oracle_util import ORIG_MC, run_oracle
     shape = (5, 2, 3, 3, 8)
-    out = os.path.join(tempfile.gettempdir(), "orig_walk_%d%d%d%d%d" % shape)
+    out = os.path.join(native_build_dir(), "orig_walk_%d%d%d%d%d" % shape)
     src = [os.path.join(ROOT, "tests", "native", "orig_walk.cpp"), os.path.join(ROOT, "raft-tla_amd", "csrc", "model.cpp"),
            os.path.join(ROOT, "raft-tla_amd", "csrc", "orig_model.cpp")]
     tmp = "%s.%d" % (out, os.getpid())
