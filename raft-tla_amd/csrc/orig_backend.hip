@@ -28,7 +28,8 @@
 //  5. orig_materialize workgroup per 256 parents: winners in key order (parent-major, instance
 //     order), re-derived from (parent, instance), stored with their parent pointers at their
 //     FIFO position; invariants of the new states.
-//  6. orig_advance   the level's running count of new states.
+//  6. orig_advance   the level's running count of new states (between the chunks of a level; the
+//     host adds the last chunk's count itself).
 //
 // The first *event* of a level in key order — a TLC evaluation error while computing a
 // parent's successors, a deadlock, an invariant violation (new or out-of-model successor) — is
@@ -1045,6 +1046,60 @@ __global__ void orig_reset_ctr(unsigned long long* ctr) {
   for (int t = threadIdx.x; t < K_NCTR; t += blockDim.x) ctr[t] = t == K_EVENT ? ~0ull : 0ull;
 }
 
+// run start: the initial state (global id 0), its meta word (no parent) and its seen-set entry
+// (key 0), written on the run's stream so that nothing at run start blocks the host
+template <int NWP>
+struct InitWords { u32 w[NWP]; };
+template <int NWP, int STRIDE>
+__global__ void orig_init_state(InitWords<NWP> s0, u32* states, u64* meta, u64* table, u64 mask, u64 fp) {
+  if (threadIdx.x < NWP) states[threadIdx.x] = s0.w[threadIdx.x];
+  if (threadIdx.x == 0) {
+    meta[0] = ~0ull;
+    const u64 pos = fp & mask;
+    table[STRIDE * pos] = fp;
+    if (STRIDE == 2) table[2 * pos + 1] = ~0ull;
+  }
+}
+
+// The seen-set moves from the starter table to the (just cleared) full table: every occupied
+// starter entry is inserted by linear probing with CAS.  Runs alone on the stream, between two
+// levels; the starter holds each fingerprint once, so an inserted entry belongs to one lane and
+// its ~key word (STRIDE 2: TLC's FIFO order) is a plain store.  moved (may be null): entries moved.
+template <int STRIDE>
+__global__ void __launch_bounds__(BS) orig_migrate(const u64* src, u64 n, u64* dst, u64 mask, unsigned long long* ctr,
+                                                   unsigned long long* moved) {
+  constexpr int E = 4 / STRIDE;   // entries per 32-B group: the walk is a stream of 16-B loads (n is a multiple of E)
+  u32 mine = 0, err = 0;
+#pragma unroll 2
+  for (u64 g = (u64)blockIdx.x * BS + threadIdx.x; g < n / E; g += (u64)gridDim.x * BS) {
+    const ulonglong2* p = reinterpret_cast<const ulonglong2*>(src + 4 * g);
+    const ulonglong2 lo = p[0], hi = p[1];
+    const u64 v[4] = {lo.x, lo.y, hi.x, hi.y};
+#pragma unroll
+    for (int j = 0; j < E; ++j) {
+      const u64 fp = v[STRIDE * j], nk = STRIDE == 2 ? v[2 * j + 1] : 0ull;
+      if (!fp) continue;
+      ++mine;
+      u64 slot = fp & mask;
+      for (u64 probe = 0;; ++probe) {
+        if (probe > mask || probe >= (1u << 20)) { err |= OE_TABLE_FULL; break; }   // as probe_batch
+        if (dst[STRIDE * slot] == 0ull &&
+            atomicCAS((unsigned long long*)&dst[STRIDE * slot], 0ull, (unsigned long long)fp) == 0ull) {
+          if (STRIDE == 2) dst[2 * slot + 1] = nk;
+          break;
+        }
+        slot = (slot + 1) & mask;
+      }
+    }
+  }
+  if (err) atomicOr(&ctr[K_ERR], (unsigned long long)err);
+  if (moved) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) mine += __shfl_xor(mine, d);
+    if (__lane_id() == 0 && mine) atomicAdd(moved, (unsigned long long)mine);
+  }
+}
+
 // ------------------------------------------------------------------ TLC's stop point
 // On the level's first event (parent gid_stop, instance k_stop, kind): TLC's generated counts
 // are the whole successor lists of the parents before it and of the event's parent (none when
@@ -1339,8 +1394,9 @@ class OrigGpu : public Backend {
 
   int observed_collision(double& v, std::string& err) override {
     if (!d_table_ || alloc_world_ != 0) { err = "after a single-GPU mc_run only"; return MC_E_STATE; }
-    return last_fifo_ ? fpgap::observed(d_table_, table_mask_ + 1, 2, stream_, v, err)
-                      : fpgap::observed(d_table_, 2 * (table_mask_ + 1), 1, stream_, v, err);
+    if (!run_table_) { err = "after a single-GPU mc_run only"; return MC_E_STATE; }
+    // the table the run ended on: the starter, when the model never outgrew it
+    return fpgap::observed(run_table_, run_mask_ + 1, last_fifo_ ? 2 : 1, stream_, v, err);
   }
 
   std::string describe_json() const override {
@@ -1406,7 +1462,35 @@ class OrigGpu : public Backend {
     }
     HIPCHK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
     for (auto& e : ev_) HIPCHK(hipEventCreate(&e));
+    HIPCHK(hipEventCreateWithFlags(&ctr_ev_, hipEventDisableTiming));
+    if (world == 0) {   // single-GPU run(): the full table's clear runs on a stream of its own beside the first levels
+      HIPCHK(hipStreamCreateWithFlags(&clear_stream_, hipStreamNonBlocking));
+      HIPCHK(hipEventCreateWithFlags(&clear_ev_, hipEventDisableTiming));
+      if (2 * slots >= STARTER_FACTOR * STARTER_SLOTS)
+        if (int rc = ensure_starter(STARTER_SLOTS, err)) return rc;
+    }
     dev_ = o.device; req_table_ = o.fp_table_bytes; req_store_ = o.state_store_bytes; alloc_world_ = world;
+    return 0;
+  }
+
+  // The starter seen-set: a small table the search begins on while the full table's clear (pure
+  // bandwidth, 1.4 ms for 4 GiB) runs on clear_stream_ beside the first levels (pure launch
+  // latency).  STARTER_SLOTS entries of the run's layout (8 B, or 16 B in FIFO order), used when
+  // the full table has at least STARTER_FACTOR times as many; RAFTMC_STARTER_SLOTS (read per run):
+  // 0 = no starter, a power of two = that many slots whatever the full table's size.
+  // 2^23 slots (profiles/r07_overlap_ab.txt): C2 leaves it after 8 levels, when the
+  // 4 GiB clear has just ended, and its own clear and orig_migrate's walk (64 MiB each) are the
+  // cheapest; 2^24 and 2^25 stay one level longer, 2^26 two, and pay 2x to 8x for both.
+  static constexpr u64 STARTER_SLOTS = 1ull << 23, STARTER_FACTOR = 8;
+  int ensure_starter(u64 slots, std::string& err) {
+    if (d_starter_ && starter_cap_ == slots) return 0;
+    if (d_starter_) {
+      HIPCHK(hipStreamSynchronize(stream_));
+      HIPCHK(hipFree(d_starter_));
+      d_starter_ = nullptr; starter_cap_ = 0;
+    }
+    HIPCHK(hipMalloc(&d_starter_, slots * 16));
+    starter_cap_ = slots;
     return 0;
   }
 
@@ -1451,15 +1535,44 @@ class OrigGpu : public Backend {
     unstored_ = 0;   // a previous run's unstored level must not outlive it (mc_dump_states)
     if (int rc = ensure_alloc(o, 0, err)) return rc;   // world 0 = single-GPU pipeline
     auto t0 = std::chrono::steady_clock::now();
-    HIPCHK(hipMemsetAsync(d_table_, 0, (table_mask_ + 1) * 16, stream_));
-    HIPCHK(hipStreamSynchronize(stream_));
     // TLC -workers 1: single-worker FIFO order (16-B {fp, ~key} entries); -workers N: 8-B entries
     const bool fifo = o.workers == 1;
     last_fifo_ = fifo;
     // RAFTMC_COUNT_PROBES: count the seen-set probes of the -workers N pipeline (an instrumented
     // kernel; read per run, so a caller can count in a run of its own outside a timed region)
     const bool count_probes = std::getenv("RAFTMC_COUNT_PROBES") != nullptr;
-    const u64 tmask = fifo ? table_mask_ : 2 * (table_mask_ + 1) - 1;
+    const u64 full_mask = fifo ? table_mask_ : 2 * (table_mask_ + 1) - 1;
+    // a run that returned early on the starter may have left the full table's clear in flight
+    HIPCHK(hipStreamSynchronize(clear_stream_));
+    // the starter seen-set (ensure_starter's comment); a recovered search re-inserts every stored
+    // state first, so it starts on the full table
+    u64 st_slots = 0;
+    if (o.recover_path.empty()) {
+      if (full_mask + 1 >= STARTER_FACTOR * STARTER_SLOTS) st_slots = STARTER_SLOTS;
+      if (const char* sv = std::getenv("RAFTMC_STARTER_SLOTS")) {
+        char* end = nullptr;
+        const unsigned long long v = std::strtoull(sv, &end, 0);
+        if (end != sv && *end == 0 && (v & (v - 1)) == 0 && (v == 0 || (v >= 64 && v <= (1ull << 32)))) st_slots = v;
+      }
+    }
+    u64* tbl = d_table_;    // the table the search is on, and its entry mask
+    u64 tmask = full_mask;
+    if (st_slots) {
+      if (int rc = ensure_starter(st_slots, err)) return rc;
+      // the starter's clear first, alone: beside the full clear it gets only its share of the
+      // bandwidth and ends when that one does (measured: 1.03 ms for 256 MiB beside 4 GiB).  The
+      // full clear starts behind it (ctr_ev_ is free until the first level's readback).
+      HIPCHK(hipMemsetAsync(d_starter_, 0, st_slots * (fifo ? 16 : 8), stream_));
+      HIPCHK(hipEventRecord(ctr_ev_, stream_));
+      HIPCHK(hipStreamWaitEvent(clear_stream_, ctr_ev_, 0));
+      HIPCHK(hipMemsetAsync(d_table_, 0, (table_mask_ + 1) * 16, clear_stream_));
+      HIPCHK(hipEventRecord(clear_ev_, clear_stream_));
+      tbl = d_starter_; tmask = st_slots - 1;
+    } else {
+      HIPCHK(hipMemsetAsync(d_table_, 0, (table_mask_ + 1) * 16, stream_));
+      HIPCHK(hipStreamSynchronize(stream_));
+    }
+    run_table_ = tbl; run_mask_ = tmask;
     ctr_clean_ = false;
 
     r = RunResult();
@@ -1478,17 +1591,16 @@ class OrigGpu : public Backend {
     } else {
     // ---- Init (raft_original.tla:139-159): one state, generated and distinct
     u32 w0[S::NW]; S::pack(s0, w0);
-    u32 wp[NWP] = {0}; for (int q = 0; q < S::NW; ++q) wp[q] = w0[q];
+    InitWords<NWP> wp = {}; for (int q = 0; q < S::NW; ++q) wp.w[q] = w0[q];
     const u64 fp0 = fp64(w0, r.seed);
-    const u64 e0[2] = {fp0, ~0ull};   // key 0
-    if (fifo) HIPCHK(hipMemcpy(d_table_ + 2 * (fp0 & tmask), e0, 16, hipMemcpyHostToDevice));
-    else HIPCHK(hipMemcpy(d_table_ + (fp0 & tmask), e0, 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_states_, wp, NWP * 4, hipMemcpyHostToDevice));
-    const u64 nometa = ~0ull;
-    HIPCHK(hipMemcpy(d_meta_, &nometa, 8, hipMemcpyHostToDevice));
+    static_assert(NWP <= 64, "orig_init_state: one lane per state word");
+    if (fifo) hipLaunchKernelGGL((orig_init_state<NWP, 2>), dim3(1), dim3(64), 0, stream_, wp, d_states_, d_meta_, tbl, tmask, fp0);
+    else hipLaunchKernelGGL((orig_init_state<NWP, 1>), dim3(1), dim3(64), 0, stream_, wp, d_states_, d_meta_, tbl, tmask, fp0);
+    HIPCHK(hipGetLastError());
     r.generated = 1; r.distinct = 1; total_ = 1;
     r.levels.push_back({1, 1, 0.0});
     r.depth = 1;
+    if (!S::in_model(s0, m_.rt) || S::violated(s0, m_.rt.invariants)) HIPCHK(hipStreamSynchronize(stream_));   // the run ends here
     if (!S::in_model(s0, m_.rt)) { err = "the initial state violates a state constraint"; r.verdict = MC_VERDICT_OK; r.distinct = 0; return 0; }
     if (u32 bad = S::violated(s0, m_.rt.invariants)) {
       r.verdict = MC_VERDICT_INVARIANT_VIOLATION; r.violated = first_violated(bad);
@@ -1521,6 +1633,28 @@ class OrigGpu : public Backend {
       }
       ctr_clean_ = false;
       const u64 level_end = level_begin + level_count;
+      // The search stays on the starter while the states so far plus all this level can insert
+      // (level_count * NI successors) keep it at most half full, so the starter never reports a
+      // full table.  Otherwise the seen-set moves to the full table before the level is queued:
+      // the stream waits for the clear (no host wait) and orig_migrate re-inserts the entries.
+      if (tbl == d_starter_ && level_end + level_count * (u64)S::NI > st_slots / 2) {
+        HIPCHK(hipStreamWaitEvent(stream_, clear_ev_, 0));
+        unsigned long long* const moved = progress_ ? (unsigned long long*)d_stop_ : nullptr;
+        if (moved) HIPCHK(hipMemsetAsync(d_stop_, 0, 8, stream_));
+        const unsigned mblk = (unsigned)std::min<u64>(2048, (st_slots + BS - 1) / BS);
+        if (fifo) hipLaunchKernelGGL((orig_migrate<2>), dim3(mblk), dim3(BS), 0, stream_, (const u64*)d_starter_, st_slots, d_table_, full_mask, (unsigned long long*)d_ctr_, moved);
+        else hipLaunchKernelGGL((orig_migrate<1>), dim3(mblk), dim3(BS), 0, stream_, (const u64*)d_starter_, st_slots, d_table_, full_mask, (unsigned long long*)d_ctr_, moved);
+        HIPCHK(hipGetLastError());
+        if (moved) {
+          u64 n = 0;
+          HIPCHK(hipMemcpyAsync(&n, d_stop_, 8, hipMemcpyDeviceToHost, stream_));
+          HIPCHK(hipStreamSynchronize(stream_));
+          std::fprintf(stderr, "seen-set switch after level %lld: %llu entries moved from the %llu-slot starter to the full table\n",
+                       (long long)r.depth, (unsigned long long)n, (unsigned long long)st_slots);
+        }
+        tbl = d_table_; tmask = full_mask;
+        run_table_ = tbl; run_mask_ = tmask;
+      }
       // every chunk's kernels are queued without waiting: the chunk's insert and winner counts
       // stay on the device (grid-stride / scanned offsets), so the host synchronises once per
       // level, for the counters
@@ -1539,7 +1673,7 @@ class OrigGpu : public Backend {
         DedupArgs d;
         d.rfp = d_rfp_; d.rkey = d_rkey_; d.rcnt = d_rcnt_blk_; d.region = (u64)BS * S::NI; d.gid0 = cb;
         d.urec = (ulonglong2*)d_urec_; d.ucnt = d_ucnt_;
-        d.table = d_table_; d.table_mask = tmask; d.newpos = d_newrec_; d.ctr = (unsigned long long*)d_ctr_;
+        d.table = tbl; d.table_mask = tmask; d.newpos = d_newrec_; d.ctr = (unsigned long long*)d_ctr_;
         d.prof = prof_ ? 1u : 0u;
         // kernel boundaries share an event (each event record costs ~5 us of stream time)
         if (fifo) {
@@ -1558,7 +1692,7 @@ class OrigGpu : public Backend {
         HIPCHK(hipEventRecord(e[3], stream_));
         if (fifo) {
           MarkArgs mk;
-          mk.newpos = d_newrec_; mk.table = d_table_; mk.gid0 = cb; mk.chunk_count = cnt; mk.winmask = d_winmask_;
+          mk.newpos = d_newrec_; mk.table = tbl; mk.gid0 = cb; mk.chunk_count = cnt; mk.winmask = d_winmask_;
           mk.ww = WW; mk.ctr = (unsigned long long*)d_ctr_;
           hipLaunchKernelGGL(orig_mark, dim3((unsigned)std::min<u64>(2048, (cnt * 2 + BS - 1) / BS)), dim3(BS), 0, stream_, mk);
           HIPCHK(hipGetLastError());
@@ -1582,17 +1716,24 @@ class OrigGpu : public Backend {
         }
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(e[7], stream_));
-        hipLaunchKernelGGL(orig_advance, dim3(1), dim3(64), 0, stream_, (unsigned long long*)d_ctr_);
-        HIPCHK(hipGetLastError());
+        // between chunks; after the level's last chunk the host adds the two counters it reads back
+        // anyway (both paths leave the chunk's count in K_CHUNK_NEW: orig_dedup_plain / orig_scan)
+        if (cb + chunk_states_ < level_end) {
+          hipLaunchKernelGGL(orig_advance, dim3(1), dim3(64), 0, stream_, (unsigned long long*)d_ctr_);
+          HIPCHK(hipGetLastError());
+        }
         for (size_t q = 0; q < r.kernels.size(); ++q) if (fifo || q != 2) r.kernels[q].launches += 1;
         r.kernels[0].algo_bytes += (double)cnt * S_B;        // + G_in * 10 record bytes per level below
       }
       u64* const c = h_ctr_;   // pinned: the readback is one direct copy
       HIPCHK(hipMemcpyAsync(c, d_ctr_, K_NCTR * 8, hipMemcpyDeviceToHost, stream_));
+      HIPCHK(hipEventRecord(ctr_ev_, stream_));
       hipLaunchKernelGGL(orig_reset_ctr, dim3(1), dim3(64), 0, stream_, (unsigned long long*)d_ctr_);
       HIPCHK(hipGetLastError());
       ctr_clean_ = true;
-      HIPCHK(hipStreamSynchronize(stream_));
+      // the host waits for the copy alone (the level's kernel events were all recorded before it):
+      // the reset behind it runs while the host looks at the counters
+      HIPCHK(hipEventSynchronize(ctr_ev_));
       double level_ms = 0;
       for (int q = 0; q < nch; ++q) {
         // event pairs per kernel: generate (e0, e1), dedup (e1, e3), mark/scan (e3, e5; FIFO only),
@@ -1605,7 +1746,7 @@ class OrigGpu : public Backend {
           r.kernels[k].ms += ms; level_ms += ms;
         }
       }
-      const u64 nnew = c[K_LEVEL_NEW];
+      const u64 nnew = c[K_LEVEL_NEW] + c[K_CHUNK_NEW];   // earlier chunks (orig_advance) + the last one
       const u64 next_write = level_end + nnew;
       if (progress_)   // TLC's progress line, per BFS level (RAFTMC_PROGRESS=1), on stderr
         std::fprintf(stderr, "Progress(%lld) at %.3f s: %lld states generated, %llu distinct states found, %llu states left on queue "
@@ -2497,6 +2638,11 @@ class OrigGpu : public Backend {
   u32* d_lead_ = nullptr;      // [chunk] the chunk's leader-work parents (orig_generate -> orig_generate_lead)
   hipStream_t stream_ = nullptr;
   hipEvent_t ev_[9] = {};
+  hipEvent_t ctr_ev_ = nullptr;          // recorded behind the level's counter readback
+  // the starter seen-set (ensure_starter) and the stream / event of the full table's clear
+  u64* d_starter_ = nullptr; u64 starter_cap_ = 0;
+  hipStream_t clear_stream_ = nullptr; hipEvent_t clear_ev_ = nullptr;
+  u64* run_table_ = nullptr; u64 run_mask_ = 0;   // the table the last single-GPU run ended on (entries - 1)
   u64 table_mask_ = 0, cap_ = 0, total_ = 0, chunk_states_ = 0;
   u64 unstored_ = 0;   // states of the last level counted but not stored (count_final_level)
   int dev_ = -1, alloc_world_ = 0; uint64_t req_table_ = 0, req_store_ = 0;
@@ -2527,6 +2673,13 @@ class OrigGpu : public Backend {
 
   void release_device() override { release(); }
   void release() {
+    // a run that returned early may have left the full table's clear in flight
+    if (clear_stream_) { (void)hipStreamSynchronize(clear_stream_); (void)hipStreamDestroy(clear_stream_); clear_stream_ = nullptr; }
+    if (stream_) (void)hipStreamSynchronize(stream_);
+    if (clear_ev_) { (void)hipEventDestroy(clear_ev_); clear_ev_ = nullptr; }
+    if (ctr_ev_) { (void)hipEventDestroy(ctr_ev_); ctr_ev_ = nullptr; }
+    if (d_starter_) { (void)hipFree(d_starter_); d_starter_ = nullptr; starter_cap_ = 0; }
+    run_table_ = nullptr; run_mask_ = 0;
     for (void* p : {(void*)d_table_, (void*)d_states_, (void*)d_meta_, (void*)d_ctr_, (void*)d_stop_, (void*)d_rfp_, (void*)d_rkey_,
                     (void*)d_rcnt_blk_, (void*)d_newrec_, (void*)d_winmask_, (void*)d_wcnt_, (void*)d_woff_, (void*)d_urec_, (void*)d_ucnt_,
                     (void*)d_route_, (void*)d_rcnt_, (void*)d_stout_, (void*)d_lead_})
