@@ -335,6 +335,38 @@ int mc_shard_layout(mc_ctx* ctx, const int64_t* frontier_counts);
 int mc_shard_select(mc_ctx* ctx, int64_t* reply_counts);
 int mc_shard_event_stats(mc_ctx* ctx, const int64_t* global_stats, int64_t* stats);
 
+/* ---------------------------------------------------------------------------------------------
+ * Simulation mode (TLC's -simulate; thirdparty/raft_original.tla, hand-compiled, only).
+ * mc_set_simulate(ctx, num_walks, batch): the next mc_run runs `num_walks` seeded random walks
+ * (numbered 0 .. num_walks - 1, each from Init) instead of a BFS, `batch` walkers per kernel
+ * launch (0: the default, 262144); num_walks <= 0 turns simulation off again.  mc_opts.max_depth
+ * is the walk length in states, Init included (TLC's -depth; 0 = 100, TLC's default in this
+ * mode), mc_opts.seed the walks' seed.  Every step evaluates all action instances (each enabled
+ * one counts as generated, per action), checks the invariants on every generated successor
+ * (in-model ones only with MC_COMPAT_INV_OUT_OF_MODEL cleared) and moves to one in-model successor
+ * chosen uniformly by counter-based random numbers, so a walk is a function of (seed, walk) alone.
+ * The run stops after the first batch that records an event and reports that batch's minimum
+ * (trace length, walk, instance); the results are a function of (model, cfg, seed, num_walks,
+ * depth, batch) only.  TLC's RNG stream, its choice among several violating walks and its
+ * progress lines are not reproduced.
+ * Summary of a simulation: generated = successors evaluated, distinct = left_on_queue = 0, depth =
+ * the longest walk in states, no levels, per-action generated counts (distinct 0); the trace and
+ * the exit code as after a BFS (12 for an invariant violation).
+ * Refused: any other spec family or the generated path (MC_E_UNSUPPORTED; never a silent BFS),
+ * a handle with a checkpoint or recover path, n_gpus > 1 or count_final_level (MC_E_UNSUPPORTED);
+ * mc_set_checkpoint / mc_set_recover and every mc_shard_* call on a handle with simulation on
+ * (MC_E_UNSUPPORTED); mc_dump_states and mc_collision_observed after a simulation (MC_E_STATE:
+ * there is no store and no seen-set).
+ * mc_sim_stats: walks run (whole batches), states expanded over all walks, the event's walk
+ * (-1: no event), after a simulation run (MC_E_STATE otherwise).
+ * mc_sim_walk: walk `walk` replayed from (seed, walk) with the handle's depth and flags, one
+ * canonical line per state (the form mc_dump_states writes); a walk that ends in a violation has
+ * the violating state as its last line.  Needs no run; caller frees with mc_free.
+ * ------------------------------------------------------------------------------------------- */
+int mc_set_simulate(mc_ctx* ctx, int64_t num_walks, int64_t batch);
+int mc_sim_stats(const mc_ctx* ctx, int64_t* walks_run, int64_t* steps, int64_t* event_walk);
+int mc_sim_walk(mc_ctx* ctx, int64_t walk, char** text, size_t* len);
+
 #ifdef __cplusplus
 }
 #endif

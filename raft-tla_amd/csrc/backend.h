@@ -39,6 +39,10 @@ struct RunOpts {
   // mc_opts.count_final_level: the last level of a depth-bounded -workers N search is counted and
   // checked, not stored (raft_original; ignored elsewhere)
   bool count_final_level = false;
+  // simulation mode (TLC -simulate, mc_set_simulate): sim_walks > 0 makes run() a batch of seeded
+  // random walks instead of a BFS (raft_original only); max_depth is the walk length in states
+  // (0 = 100, TLC's default), seed the walks' seed, sim_batch the walkers per launch (0 = default)
+  int64_t sim_walks = 0, sim_batch = 0;
 };
 
 struct LevelStat { int64_t states = 0, generated = 0; double kernel_ms = 0; };
@@ -62,6 +66,9 @@ struct RunResult {
   int state_bytes = 0;
   int n_launches = 0;
   std::vector<KernelStat> kernels;       // per-kernel HIP-event time and algorithmic bytes
+  // simulation mode: walks run (whole batches), states expanded over all walks, the event's walk (-1: none)
+  bool simulated = false;
+  int64_t sim_walks_run = 0, sim_steps = 0, sim_event_walk = -1;
 };
 
 struct Backend {
@@ -70,6 +77,13 @@ struct Backend {
   virtual std::string describe_json() const = 0;
   virtual int run(const RunOpts& o, RunResult& r, std::string& err) = 0;
   virtual int dump_states(const std::string& path, std::string& err) = 0;
+  // simulation mode (RunOpts::sim_walks): only a backend that says so runs it; the others refuse
+  // (mc_set_simulate), they never fall back to a BFS
+  virtual bool supports_simulation() const { return false; }
+  // walk `walk` of a simulation with o's seed / depth / flags, one canonical line per state
+  virtual int sim_walk(const RunOpts& o, int64_t walk, std::string& text, std::string& err) {
+    (void)o; (void)walk; (void)text; err = "simulation mode is not available for this spec"; return -4;
+  }
   // mc_release_device_memory: free the device buffers kept between runs (the next run allocates again)
   virtual void release_device() = 0;
   // TLC's "based on the actual fingerprints" estimate: 1 / min gap of the seen-set (fp_gap.h)

@@ -204,6 +204,7 @@ int mc_set_history_prefix(mc_ctx* c, const char* constraint, const char* trace_t
 int mc_set_checkpoint(mc_ctx* c, const char* path, int32_t every_levels) {
   if (!c || every_levels < 0) return MC_E_INVALID;
   if (!c->be) return MC_E_STATE;
+  if (path && c->ro.sim_walks > 0) { c->last_error = "simulation mode keeps no BFS state: no checkpoints"; return MC_E_UNSUPPORTED; }
   if (path && c->ro.count_final_level) {   // a checkpoint must hold every level it names
     c->last_error = "checkpoints store every level: not with count_final_level";
     return MC_E_UNSUPPORTED;
@@ -216,6 +217,7 @@ int mc_set_checkpoint(mc_ctx* c, const char* path, int32_t every_levels) {
 int mc_set_recover(mc_ctx* c, const char* path) {
   if (!c) return MC_E_INVALID;
   if (!c->be) return MC_E_STATE;
+  if (path && c->ro.sim_walks > 0) { c->last_error = "simulation mode starts every walk from Init: nothing to recover"; return MC_E_UNSUPPORTED; }
   c->ro.recover_path = path ? path : "";
   return MC_OK;
 }
@@ -339,6 +341,9 @@ int mc_run(mc_ctx* c) {
   if (!c) return MC_E_INVALID;
   if (!c->be) return MC_E_STATE;
   c->released = false;
+  if (c->ro.sim_walks > 0) {   // mc_set_simulate checked these; they cannot have changed since
+    if (c->n_gpus > 1 || !c->be->supports_simulation()) { c->ran = false; c->last_error = "simulation mode: one GPU, raft_original only"; return MC_E_UNSUPPORTED; }
+  }
   if (c->n_gpus > 1) { c->ran = false; return run_multi(c); }
   std::string err;
   int rc = c->be->run(c->ro, c->res, err);
@@ -421,6 +426,8 @@ int mc_report(const mc_ctx* c, char** text, size_t* len) {
     if (!r.trace.empty()) o << "Error: The behavior up to this point is:\n" << trace_text(c, r);
   } else if (r.verdict == MC_VERDICT_CAPACITY_OVERFLOW) {
     o << "Error: " << r.error << "\n";
+  } else if (r.verdict == MC_VERDICT_OK && r.simulated) {
+    o << "Simulation completed. No error has been found.\n";
   } else if (r.verdict == MC_VERDICT_OK) {
     o << "Model checking completed. No error has been found.\n";
     o << "  Estimates of the probability that TLC did not check all reachable states\n";
@@ -433,8 +440,14 @@ int mc_report(const mc_ctx* c, char** text, size_t* len) {
       o << buf;
     }
   }
+  if (r.simulated) {
+    o << r.sim_walks_run << " walks of at most " << (c->ro.max_depth > 0 ? c->ro.max_depth : 100) << " states, " << r.sim_steps
+      << " steps, " << r.generated << " states generated.\n";
+    o << "The longest walk has " << r.depth << " states.\n";
+  } else {
   o << r.generated << " states generated, " << r.distinct << " distinct states found, " << r.left_on_queue << " states left on queue.\n";
   o << "The depth of the complete state graph search is " << r.depth << ".\n";
+  }
   o << "Finished in " << (long long)(r.seconds_total * 1000.0 + 0.5) << "ms\n";
   o << "Verdict: " << verdict_name(r.verdict) << "\n";
   *text = dup_text(o.str(), len);
@@ -464,6 +477,7 @@ int mc_release_device_memory(mc_ctx* c) {
 int mc_collision_observed(mc_ctx* c, double* val) {
   if (!c || !val) return MC_E_INVALID;
   if (!c->ran || c->released) return MC_E_STATE;
+  if (c->res.simulated) { c->last_error = "a simulation has no seen-set"; return MC_E_STATE; }
   std::string err;
   double v = -1;
   const int rc = c->be->observed_collision(v, err);
@@ -476,6 +490,7 @@ int mc_collision_observed(mc_ctx* c, double* val) {
 int mc_dump_states(const mc_ctx* c, const char* path) {
   if (!c || !path) return MC_E_INVALID;
   if (!c->ran || c->released) return MC_E_STATE;
+  if (c->res.simulated) { const_cast<mc_ctx*>(c)->last_error = "a simulation stores no states"; return MC_E_STATE; }
   std::string err;
   if (c->n_gpus > 1) {
     // every rank's partition of the state space: one file per rank, path.rank<r> (as shard.py writes)
@@ -523,6 +538,10 @@ int mc_exit_code(const mc_ctx* c) {
   if (!c->be) return MC_E_STATE; \
   if (!c->ro.checkpoint_path.empty() || !c->ro.recover_path.empty()) { \
     c->last_error = "checkpoint/recover apply to single-GPU runs (mc_run); a sharded run cannot use them"; \
+    return MC_E_UNSUPPORTED; \
+  } \
+  if (c->ro.sim_walks > 0) { \
+    c->last_error = "simulation mode runs on one GPU (mc_run); a sharded run cannot use it"; \
     return MC_E_UNSUPPORTED; \
   }
 #define SHARD_RC(expr)                      \
@@ -666,6 +685,10 @@ int mc_shard_run_loopback(mc_ctx* const* ctxs, int32_t world) {
       ctxs[r]->last_error = "checkpoint/recover apply to single-GPU runs (mc_run); a sharded run cannot use them";
       return MC_E_UNSUPPORTED;
     }
+    if (ctxs[r]->ro.sim_walks > 0) {
+      ctxs[r]->last_error = "simulation mode runs on one GPU (mc_run); a sharded run cannot use it";
+      return MC_E_UNSUPPORTED;
+    }
   }
   rmc::LoopbackWorld w(world);
   std::vector<int> rcs(world, MC_OK);
@@ -688,6 +711,42 @@ int mc_shard_run_loopback(mc_ctx* const* ctxs, int32_t world) {
   for (auto& x : th) x.join();
   for (int r = 0; r < world; ++r) if (rcs[r]) return rcs[r];
   return MC_OK;
+}
+
+// ------------------------------------------------------------------ simulation mode (TLC -simulate)
+int mc_set_simulate(mc_ctx* c, int64_t num_walks, int64_t batch) {
+  if (!c) return MC_E_INVALID;
+  if (!c->be) return MC_E_STATE;
+  if (num_walks <= 0) { c->ro.sim_walks = 0; c->ro.sim_batch = 0; return MC_OK; }
+  if (batch < 0) return MC_E_INVALID;
+  auto refuse = [&](const char* why) { c->last_error = why; return MC_E_UNSUPPORTED; };
+  if (!c->be->supports_simulation())
+    return refuse("simulation mode (-simulate) exists for thirdparty/raft_original.tla (hand-compiled) only; this spec is not run "
+                  "as a BFS instead");
+  if (!c->ro.checkpoint_path.empty() || !c->ro.recover_path.empty()) return refuse("simulation mode: not with a checkpoint or recover path");
+  if (c->n_gpus > 1) return refuse("simulation mode runs on one GPU (n_gpus = 1)");
+  if (c->ro.count_final_level) return refuse("simulation mode: not with count_final_level");
+  c->ro.sim_walks = num_walks; c->ro.sim_batch = batch;
+  return MC_OK;
+}
+
+int mc_sim_stats(const mc_ctx* c, int64_t* walks_run, int64_t* steps, int64_t* event_walk) {
+  if (!c) return MC_E_INVALID;
+  if (!c->ran || !c->res.simulated) return MC_E_STATE;
+  if (walks_run) *walks_run = c->res.sim_walks_run;
+  if (steps) *steps = c->res.sim_steps;
+  if (event_walk) *event_walk = c->res.sim_event_walk;
+  return MC_OK;
+}
+
+int mc_sim_walk(mc_ctx* c, int64_t walk, char** text, size_t* len) {
+  if (!c || !text) return MC_E_INVALID;
+  if (!c->be) return MC_E_STATE;
+  std::string t, err;
+  const int rc = c->be->sim_walk(c->ro, walk, t, err);
+  if (rc) { c->last_error = err; return rc; }
+  *text = dup_text(t, len);
+  return *text ? MC_OK : MC_E_OOM;
 }
 
 #ifndef RAFTMC_SOURCE_HASH

@@ -57,6 +57,7 @@
 #include "orig_text.h"
 #include "rccl_api.h"
 #include "shard_transport.h"
+#include "sim_rng.h"
 
 namespace rmc {
 
@@ -1376,6 +1377,8 @@ __global__ void __launch_bounds__(BS) orig_reinsert(const u32* states, u64 n, u6
   if (err) atomicOr(&ctr[K_ERR], (unsigned long long)err);
 }
 
+#include "orig_sim.hip"   // simulation mode: the walker kernel and the host replay of one walk
+
 #define HIPCHK(x)                                                                             \
   do {                                                                                        \
     hipError_t e_ = (x);                                                                      \
@@ -1531,7 +1534,129 @@ class OrigGpu : public Backend {
     return ra;
   }
 
+  // ---------------------------------------------------------------- simulation mode (orig_sim.hip)
+  bool supports_simulation() const override { return true; }
+
+  static u32 sim_depth(const RunOpts& o) { return (u32)(o.max_depth > 0 ? o.max_depth : SIM_DEFAULT_DEPTH); }
+  static int sim_check(const RunOpts& o, std::string& err) {
+    if (o.max_depth > SIM_MAX_DEPTH) { err = "simulation: depth is at most " + std::to_string(SIM_MAX_DEPTH); return MC_E_INVALID; }
+    if (o.sim_walks > SIM_MAX_WALKS) { err = "simulation: at most 2^40 walks"; return MC_E_INVALID; }
+    if (o.sim_batch < 0 || o.sim_batch > (1ll << 30)) { err = "simulation: batch out of range"; return MC_E_INVALID; }
+    return 0;
+  }
+
+  int sim_walk(const RunOpts& o, int64_t walk, std::string& text, std::string& err) override {
+    if (int rc = sim_check(o, err)) return rc;
+    if (walk < 0 || walk >= SIM_MAX_WALKS) { err = "simulation: walk number out of range"; return MC_E_INVALID; }
+    SimWalk<S> w;
+    sim_replay<S>(m_.rt, o.inv_out_of_model, o.check_deadlock, o.seed, (u64)walk, sim_depth(o), w);
+    text.clear();
+    for (const W& st : w.states) { text += state_text(st, false); text += "\n"; }
+    return 0;
+  }
+
+  // RunOpts::sim_walks random walks in batches of sim_batch walkers, one orig_simulate launch per
+  // batch; the run stops after the first batch that records an event.  Allocates the counters only:
+  // no seen-set, no store (the BFS buffers of an earlier run() of this handle are left alone).
+  int simulate(const RunOpts& o, RunResult& r, std::string& err) {
+    if (int rc = sim_check(o, err)) return rc;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= o.device) { err = "no HIP device available (raftmc has no CPU fallback)"; return MC_E_NO_DEVICE; }
+    HIPCHK(hipSetDevice(o.device));
+    const auto t0 = std::chrono::steady_clock::now();
+    const u32 depth = sim_depth(o);
+    const u64 num = (u64)o.sim_walks, batch = (u64)(o.sim_batch ? o.sim_batch : SIM_DEFAULT_BATCH);
+    r = RunResult();
+    r.simulated = true;
+    r.seed = o.seed;
+    r.state_bytes = NWP * 4;
+    for (int k = 0; k < OA_NACT; ++k) r.action_names.push_back(kOrigActNames[k]);
+    r.act_generated.assign(OA_NACT, 0); r.act_distinct.assign(OA_NACT, 0);
+    r.kernels = {{"orig_simulate", 0, 0, 0}};
+    W s0; S::init(s0);
+    r.depth = 1;   // generated: the successors evaluated along the walks (Init is not counted)
+    if (!S::in_model(s0, m_.rt)) { err = "the initial state violates a state constraint"; r.verdict = MC_VERDICT_OK; return 0; }
+    if (u32 bad = S::violated(s0, m_.rt.invariants)) {
+      r.verdict = MC_VERDICT_INVARIANT_VIOLATION; r.violated = first_violated(bad);
+      r.trace.push_back({"<Initial predicate>", state_text(s0, true)});
+      r.seconds_total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+      return 0;
+    }
+    // device counters, freed on every way out
+    struct Dev {
+      unsigned long long* ctr = nullptr; hipEvent_t e0 = nullptr, e1 = nullptr;
+      ~Dev() { if (ctr) (void)hipFree(ctr); if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
+    } d;
+    HIPCHK(hipMalloc(&d.ctr, SK_NCTR * 8));
+    HIPCHK(hipEventCreate(&d.e0));
+    HIPCHK(hipEventCreate(&d.e1));
+    u64 h[SK_NCTR], event = ~0ull, maxlen = 1;
+    for (u64 w0 = 0; w0 < num && event == ~0ull; w0 += batch) {
+      const u64 n = std::min<u64>(batch, num - w0);
+      std::memset(h, 0, sizeof h);
+      h[SK_EVENT] = ~0ull;
+      HIPCHK(hipMemcpy(d.ctr, h, sizeof h, hipMemcpyHostToDevice));
+      SimArgs a;
+      a.walk0 = w0; a.nwalks = n; a.seed = o.seed; a.depth = depth; a.rt = m_.rt;
+      a.inv_oom = o.inv_out_of_model ? 1u : 0u; a.deadlock = o.check_deadlock ? 1u : 0u; a.ctr = d.ctr;
+      HIPCHK(hipEventRecord(d.e0, nullptr));
+      hipLaunchKernelGGL((orig_simulate<S>), dim3((unsigned)((n + BS - 1) / BS)), dim3(BS), 0, nullptr, a);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipEventRecord(d.e1, nullptr));
+      HIPCHK(hipMemcpy(h, d.ctr, sizeof h, hipMemcpyDeviceToHost));
+      float ms = 0;
+      HIPCHK(hipEventElapsedTime(&ms, d.e0, d.e1));
+      r.kernels[0].ms += ms; r.kernels[0].launches += 1; r.n_launches += 1;
+      r.seconds_kernels += ms * 1e-3;
+      r.sim_walks_run += (int64_t)n;
+      r.sim_steps += (int64_t)h[SK_STEPS];
+      for (int k = 0; k < OA_NACT; ++k) { r.act_generated[k] += (int64_t)h[SK_ACT + k]; r.generated += (int64_t)h[SK_ACT + k]; }
+      maxlen = std::max<u64>(maxlen, h[SK_MAXLEN]);
+      if (progress_)
+        std::fprintf(stderr, "simulation: walks %llu..%llu, %llu steps, %.3f ms\n", (unsigned long long)w0,
+                     (unsigned long long)(w0 + n - 1), (unsigned long long)h[SK_STEPS], ms);
+      if (h[SK_ERR]) {
+        r.verdict = MC_VERDICT_CAPACITY_OVERFLOW;
+        r.error = (h[SK_ERR] & OE_CAP_ELECTIONS) ? "elections set exceeds the compiled capacity" : "message count outside the packed range";
+        r.depth = (int64_t)maxlen;
+        r.seconds_total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        return 0;
+      }
+      event = h[SK_EVENT];
+    }
+    r.depth = (int64_t)maxlen;
+    if (event != ~0ull) {
+      // the winning walk again, on the host, with the same spec code and draws
+      const u64 walk = sim_event_walk(event);
+      SimWalk<S> w;
+      sim_replay<S>(m_.rt, o.inv_out_of_model, o.check_deadlock, o.seed, walk, depth, w);
+      if (w.event != event) {
+        err = "simulation: the host replay of walk " + std::to_string(walk) + " does not reproduce the device's event";
+        return MC_E_STATE;
+      }
+      r.sim_event_walk = (int64_t)walk;
+      const u32 kind = sim_event_kind(event);
+      if (kind == EV_VIOLATION) {
+        r.verdict = MC_VERDICT_INVARIANT_VIOLATION;
+        r.violated = first_violated(S::violated(w.states.back(), m_.rt.invariants));
+      } else if (kind == EV_DEADLOCK) {
+        r.verdict = MC_VERDICT_DEADLOCK;
+      } else {
+        r.verdict = MC_VERDICT_EVAL_ERROR;
+        r.error = "TLC evaluation error while computing the successors of the last state of walk " + std::to_string(walk) +
+                  ": log[i][prevLogIndex] applied outside its domain (raft_original.tla:207-210)";
+      }
+      for (size_t k = 0; k < w.states.size(); ++k)
+        r.trace.push_back({k == 0 ? std::string("<Initial predicate>") : std::string(kOrigActNames[w.acts[k - 1]]), state_text(w.states[k], true)});
+    } else {
+      r.verdict = MC_VERDICT_OK;
+    }
+    r.seconds_total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return 0;
+  }
+
   int run(const RunOpts& o, RunResult& r, std::string& err) override {
+    if (o.sim_walks > 0) return simulate(o, r, err);   // TLC -simulate: random walks, not a BFS
     unstored_ = 0;   // a previous run's unstored level must not outlive it (mc_dump_states)
     if (int rc = ensure_alloc(o, 0, err)) return rc;   // world 0 = single-GPU pipeline
     auto t0 = std::chrono::steady_clock::now();

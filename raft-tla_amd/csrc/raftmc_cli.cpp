@@ -2,7 +2,10 @@
 //   raftmc [-config F.cfg] [-workers N] [-deadlock] [-depth D] [-device K]
 //          [-fptable BYTES] [-store BYTES] [-seed S] [-no-inv-oom] [-no-disjunct-copies] [-dump FILE] [-json]
 //          [-checkpoint LEVELS] [-checkpoint-file FILE] [-recover FILE] [-symmetry tlc|orbit]
-//          [-gpus N] [-countfinal] F.tla
+//          [-gpus N] [-countfinal] [-simulate [num=N]] F.tla
+// (-simulate [num=N]: TLC's simulation mode for raft_original -- N seeded random walks of at most
+// -depth states (default 100) with -seed S, invariants checked along each walk.  Without num= TLC
+// runs until interrupted; raftmc runs one batch, 262144 walks.  -aril is not supported.)
 // (-countfinal, with -depth D and -workers N: the states at depth D are counted and checked, not
 // stored; mc_opts.count_final_level)
 // (-gpus N: the node's GPUs -device .. -device+N-1 share one search, owner-partitioned fingerprints,
@@ -24,7 +27,8 @@ int main(int argc, char** argv) {
   mc_default_opts(&o);
   std::string tla, cfg, dump, ckpt_file = "states/raftmc.ckpt", recover;
   int ckpt_every = 0;
-  bool json = false;
+  bool json = false, simulate = false;
+  long long sim_num = 262144;   // -simulate without num=: one batch
   for (int a = 1; a < argc; ++a) {
     std::string k = argv[a];
     auto val = [&]() -> const char* {
@@ -53,6 +57,14 @@ int main(int argc, char** argv) {
       else if (v == "orbit") o.tlc_compat_flags &= ~MC_COMPAT_SYM_TLC;
       else { std::fprintf(stderr, "-symmetry tlc|orbit\n"); return 2; }
     }
+    else if (k == "-simulate") {
+      simulate = true;
+      if (a + 1 < argc && std::strncmp(argv[a + 1], "num=", 4) == 0) {
+        sim_num = std::atoll(argv[++a] + 4);
+        if (sim_num <= 0) { std::fprintf(stderr, "-simulate num=N needs N > 0\n"); return 2; }
+      }
+    }
+    else if (k == "-aril") { std::fprintf(stderr, "-aril is not supported: the walks' random numbers are counter-based (-seed)\n"); return 2; }
     else if (k == "-dump") dump = val();
     else if (k == "-json") json = true;
     else if (k == "-checkpoint") ckpt_every = std::atoi(val());
@@ -61,7 +73,12 @@ int main(int argc, char** argv) {
     else if (!k.empty() && k[0] == '-') { std::fprintf(stderr, "unknown option %s\n", k.c_str()); return 2; }
     else tla = k;
   }
-  if (tla.empty()) { std::fprintf(stderr, "usage: raftmc [-config F.cfg] [options] F.tla\n"); return 2; }
+  if (tla.empty()) {
+    std::fprintf(stderr, "usage: raftmc [-config F.cfg] [options] F.tla\n"
+                         "  -simulate [num=N]  N random walks of at most -depth states (default 100), seeded by -seed;\n"
+                         "                     without num= one batch of 262144 walks (TLC: until interrupted)\n");
+    return 2;
+  }
   if (cfg.empty()) { cfg = tla.substr(0, tla.size() > 4 ? tla.size() - 4 : tla.size()) + ".cfg"; }
   mc_ctx* c = nullptr;
   int rc = mc_open(tla.c_str(), cfg.c_str(), &o, &c);
@@ -71,6 +88,7 @@ int main(int argc, char** argv) {
     rc = mc_set_checkpoint(c, ckpt_file.c_str(), ckpt_every);
   }
   if (!rc && !recover.empty()) rc = mc_set_recover(c, recover.c_str());
+  if (!rc && simulate) rc = mc_set_simulate(c, sim_num, 0);
   if (rc) { std::fprintf(stderr, "raftmc: %s (code %d)\n", mc_last_error(c), rc); mc_close(c); return 75; }
   rc = mc_run(c);
   if (rc == 0) {   // TLC prints its fingerprint-based estimate after a completed search
@@ -83,7 +101,14 @@ int main(int argc, char** argv) {
   mc_report(c, &text, &len);
   std::fwrite(text, 1, len, stdout);
   mc_free(text);
-  if (json) {
+  int64_t sim_walks = 0, sim_steps = 0, sim_event = -1;
+  if (json && simulate && mc_sim_stats(c, &sim_walks, &sim_steps, &sim_event) == 0) {
+    mc_summary_t s; mc_summary(c, &s);
+    std::printf("{\"verdict\": %d, \"generated\": %lld, \"distinct\": %lld, \"depth\": %lld, \"seconds\": %.6f, \"kernel_seconds\": %.6f, "
+                "\"walks\": %lld, \"steps\": %lld, \"event_walk\": %lld}\n",
+                s.verdict, (long long)s.generated, (long long)s.distinct, (long long)s.depth, s.seconds_total, s.seconds_kernels,
+                (long long)sim_walks, (long long)sim_steps, (long long)sim_event);
+  } else if (json) {
     mc_summary_t s; mc_summary(c, &s);
     std::printf("{\"verdict\": %d, \"generated\": %lld, \"distinct\": %lld, \"depth\": %lld, \"seconds\": %.6f, \"kernel_seconds\": %.6f}\n",
                 s.verdict, (long long)s.generated, (long long)s.distinct, (long long)s.depth, s.seconds_total, s.seconds_kernels);

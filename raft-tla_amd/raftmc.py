@@ -31,7 +31,8 @@ EXPORTS = ["mc_opts_init", "mc_default_opts", "mc_open", "mc_run", "mc_summary",
            "mc_shard_level_stats", "mc_shard_level_commit", "mc_shard_read_state", "mc_shard_violation",
            "mc_set_history_prefix", "mc_shard_layout", "mc_shard_select", "mc_shard_event_stats",
            "mc_collision_observed", "mc_rccl_unique_id", "mc_shard_run_rccl", "mc_shard_run_loopback",
-           "mc_set_checkpoint", "mc_set_recover", "mc_action_location", "mc_source_hash", "mc_set_fault_injection", "mc_release_device_memory", "mc_set_fp_slice"]
+           "mc_set_checkpoint", "mc_set_recover", "mc_action_location", "mc_source_hash", "mc_set_fault_injection", "mc_release_device_memory", "mc_set_fp_slice",
+           "mc_set_simulate", "mc_sim_stats", "mc_sim_walk"]
 
 
 class McOpts(ctypes.Structure):
@@ -124,6 +125,9 @@ def load_library(path=LIB_PATH):
     lib.mc_set_fault_injection.argtypes = [P, ctypes.c_int32, ctypes.c_int64]
     lib.mc_set_fp_slice.argtypes = [P, ctypes.c_int32]
     lib.mc_release_device_memory.argtypes = [P]
+    lib.mc_set_simulate.argtypes = [P, ctypes.c_int64, ctypes.c_int64]
+    lib.mc_sim_stats.argtypes = [P, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
+    lib.mc_sim_walk.argtypes = [P, ctypes.c_int64, ctypes.POINTER(P), ctypes.POINTER(ctypes.c_size_t)]
     lib.mc_exit_code.argtypes = [P]
     lib.mc_free.argtypes = [P]
     lib.mc_close.argtypes = [P]
@@ -289,6 +293,35 @@ class ModelChecker:
                       error=self.lib.mc_last_error(self.h).decode(),
                       exit_code=self.lib.mc_exit_code(self.h))
 
+    def simulate(self, num_walks, batch=0):
+        """TLC -simulate (raft_original): `num_walks` seeded random walks of at most max_depth states
+        (0 = 100) from the handle's seed, `batch` walkers per launch (0 = the default).  Returns the
+        usual Result plus walks, steps and event_walk (-1: no event).  Simulation stays on for this
+        handle until simulate(0)."""
+        rc = self.lib.mc_set_simulate(self.h, num_walks, batch)
+        if rc:
+            raise RaftMCError(rc, self.lib.mc_last_error(self.h).decode())
+        if num_walks <= 0:
+            return None
+        res = self.run()
+        w, st, ev = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        rc = self.lib.mc_sim_stats(self.h, ctypes.byref(w), ctypes.byref(st), ctypes.byref(ev))
+        if rc:
+            raise RaftMCError(rc, self.lib.mc_last_error(self.h).decode())
+        res.walks, res.steps, res.event_walk = w.value, st.value, ev.value
+        return res
+
+    def sim_walk(self, walk):
+        """Walk `walk` of a simulation with the handle's seed and depth, replayed from (seed, walk):
+        one canonical line per state."""
+        p, n = ctypes.c_void_p(), ctypes.c_size_t()
+        rc = self.lib.mc_sim_walk(self.h, walk, ctypes.byref(p), ctypes.byref(n))
+        if rc:
+            raise RaftMCError(rc, self.lib.mc_last_error(self.h).decode())
+        s = ctypes.string_at(p, n.value).decode()
+        self.lib.mc_free(p)
+        return s.splitlines()
+
     def dump_states(self, path):
         rc = self.lib.mc_dump_states(self.h, path.encode())
         if rc:
@@ -316,6 +349,8 @@ def tlc_main(argv):
     """TLC-compatible argv entry point; prints the report, returns TLC's exit code."""
     spec, config, kw = None, None, {}
     checkpoint, recover = None, None
+    simulate = None
+    argv = list(argv)
     it = iter(argv)
     for a in it:
         if a == "-config":
@@ -324,6 +359,14 @@ def tlc_main(argv):
             checkpoint = int(next(it))
         elif a == "-recover":
             recover = next(it)
+        elif a == "-simulate":                   # TLC: optional num=N follows; raftmc's default is one batch
+            simulate = 262144
+        elif a.startswith("num=") and simulate is not None:
+            simulate = int(a[4:])
+        elif a == "-seed":
+            kw["seed"] = int(next(it), 0)
+        elif a == "-aril":
+            raise ValueError("-aril is not supported: the walks' random numbers are counter-based (-seed)")
         elif a == "-workers":
             kw["workers"] = int(next(it))
         elif a == "-deadlock":
@@ -352,6 +395,6 @@ def tlc_main(argv):
             mc.set_checkpoint(path, checkpoint)
         if recover:
             mc.set_recover(recover)
-        res = mc.run()
+        res = mc.simulate(simulate) if simulate is not None else mc.run()
     print(res.report, end="")
     return res.exit_code
