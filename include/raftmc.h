@@ -367,6 +367,52 @@ int mc_set_simulate(mc_ctx* ctx, int64_t num_walks, int64_t batch);
 int mc_sim_stats(const mc_ctx* ctx, int64_t* walks_run, int64_t* steps, int64_t* event_walk);
 int mc_sim_walk(mc_ctx* ctx, int64_t walk, char** text, size_t* len);
 
+/* ---------------------------------------------------------------------------------------------
+ * Continue mode (tlc_membership/raft.tla, hand-compiled, one GPU): one BFS reports the first
+ * counterexample of EVERY invariant the cfg lists.  These semantics are raftmc's own: TLC's
+ * -continue prints every violating state; this mode reports the first violating state per
+ * invariant in TLC's single-worker FIFO order, so each witness is exactly what a plain run
+ * listing that invariant (with invariants that hold) reports: the same trace, depth and stop-point
+ * counters.
+ * mc_set_continue(ctx, on): the next mc_run runs in continue mode (on = 0: off again).  The
+ * search is the one of the cfg without INVARIANTS -- invariants never decide which states are
+ * explored, and a violating state is still enqueued.  Every new successor (and every out-of-model
+ * one with MC_COMPAT_INV_OUT_OF_MODEL) is evaluated against each invariant that has no witness
+ * yet, one by one; the witness of an invariant is the violating successor with the least key
+ * (parent rank in the level * slots + slot: TLC's enumeration order) in the first level that has
+ * one, and one successor may be the witness of several invariants.  An Init state that violates
+ * an invariant is a witness of depth 1.  An invariant that fails to evaluate, a next-state error
+ * and a deadlock end the run as they end a plain run (EVAL_ERROR / DEADLOCK with the plain run's
+ * counters and trace); the witnesses before that point in key order are kept.  The run ends when
+ * every listed invariant has its witness (the summary counters are then those of the last
+ * witness's stop point), or when the space or max_depth is exhausted (the summary of the plain
+ * search without invariants).  With at least one witness and no fatal event the verdict is
+ * MC_VERDICT_INVARIANT_VIOLATION (exit code 12), and mc_summary's `violated` and mc_trace are the
+ * first witness: lowest depth, then key, then cfg position -- the plain run's counterexample.
+ * mc_report prints one "Error: Invariant X is violated." block with its trace per witness, in
+ * discovery order, before the usual summary lines.
+ * Refused with MC_E_UNSUPPORTED, by mc_set_continue where it is known then and by mc_run
+ * otherwise, never by running a plain search instead: raft_original and the generated path,
+ * n_gpus > 1, a handle with a checkpoint or recover path, simulation; mc_set_checkpoint /
+ * mc_set_recover / mc_set_simulate and every mc_shard_* call on a handle with continue mode on.
+ * mc_witness_count / mc_witness: the witnesses of the last run, in discovery order (MC_E_STATE
+ * unless the last completed run was a continue run; MC_E_INVALID for k out of range).  `trace`
+ * (may be NULL) receives the text mc_trace would give for that witness; caller frees with mc_free.
+ * act_generated / act_distinct are TLC's per-action counters at the witness's stop point, indexed
+ * like mc_action_stats (n_actions of them).
+ * ------------------------------------------------------------------------------------------- */
+typedef struct mc_witness_t {
+  char invariant[64];
+  int32_t position;              /* of the invariant in the cfg's INVARIANTS list, from 0 */
+  int32_t n_actions;
+  int64_t depth, generated, distinct, left_on_queue;
+  int64_t act_generated[32], act_distinct[32];
+  int64_t reserved[8];
+} mc_witness_t;
+int mc_set_continue(mc_ctx* ctx, int32_t on);
+int mc_witness_count(const mc_ctx* ctx, int32_t* n);
+int mc_witness(const mc_ctx* ctx, int32_t k, mc_witness_t* out, char** trace, size_t* len);
+
 #ifdef __cplusplus
 }
 #endif

@@ -43,10 +43,24 @@ struct RunOpts {
   // random walks instead of a BFS (raft_original only); max_depth is the walk length in states
   // (0 = 100, TLC's default), seed the walks' seed, sim_batch the walkers per launch (0 = default)
   int64_t sim_walks = 0, sim_batch = 0;
+  // continue mode (mc_set_continue; raftmc's own semantics): one BFS reports the first
+  // counterexample of every listed invariant instead of ending at the first violation
+  // (tlc_membership, hand-compiled, one GPU; Backend::supports_continue)
+  bool continue_mode = false;
 };
 
 struct LevelStat { int64_t states = 0, generated = 0; double kernel_ms = 0; };
 struct KernelStat { std::string name; double ms = 0, algo_bytes = 0; int64_t launches = 0; };
+
+// continue mode: the first counterexample of one listed invariant, with TLC's counters at its stop
+// point (what a plain run listing that invariant alone reports)
+struct Witness {
+  std::string invariant;
+  int position = 0;                      // of the invariant in the cfg's INVARIANTS list
+  int64_t depth = 0, generated = 0, distinct = 0, left_on_queue = 0;
+  std::vector<int64_t> act_generated, act_distinct;
+  std::vector<std::pair<std::string, std::string>> trace;
+};
 
 struct RunResult {
   int64_t generated = 0, distinct = 0, left_on_queue = 0, depth = 0;
@@ -69,6 +83,9 @@ struct RunResult {
   // simulation mode: walks run (whole batches), states expanded over all walks, the event's walk (-1: none)
   bool simulated = false;
   int64_t sim_walks_run = 0, sim_steps = 0, sim_event_walk = -1;
+  // continue mode: the witnesses in discovery order (depth, then key, then cfg position)
+  bool continued = false;
+  std::vector<Witness> witnesses;
 };
 
 struct Backend {
@@ -84,6 +101,9 @@ struct Backend {
   virtual int sim_walk(const RunOpts& o, int64_t walk, std::string& text, std::string& err) {
     (void)o; (void)walk; (void)text; err = "simulation mode is not available for this spec"; return -4;
   }
+  // continue mode (RunOpts::continue_mode): only a backend that says so runs it; the others refuse
+  // (mc_set_continue), they never run a plain search instead
+  virtual bool supports_continue() const { return false; }
   // mc_release_device_memory: free the device buffers kept between runs (the next run allocates again)
   virtual void release_device() = 0;
   // TLC's "based on the actual fingerprints" estimate: 1 / min gap of the seen-set (fp_gap.h)

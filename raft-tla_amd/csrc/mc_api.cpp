@@ -1,5 +1,6 @@
 // raftmc — C ABI implementation (include/raftmc.h).  Parses the .tla/.cfg,
 // picks the compiled spec backend, drives mc_run and renders TLC-style text.
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -71,20 +72,21 @@ const char* verdict_name(int v) {
 }
 // TLC's header: "State k: <Action line L1, col C1 to line L2, col C2 of module M>" when the
 // action's definition is found in the spec module (or a module it EXTENDS), else "<Action>"
-std::string trace_text(const mc_ctx* c, const rmc::RunResult& r) {
+std::string trace_text(const mc_ctx* c, const std::vector<std::pair<std::string, std::string>>& trace) {
   std::ostringstream o;
-  for (size_t k = 0; k < r.trace.size(); ++k) {
+  for (size_t k = 0; k < trace.size(); ++k) {
     o << "State " << (k + 1) << ": ";
     if (k == 0) o << "<Initial predicate>";
     else {
-      const std::string& loc = c->location_of(r.trace[k].first);
-      o << "<" << r.trace[k].first << (loc.empty() ? "" : " " + loc) << ">";
+      const std::string& loc = c->location_of(trace[k].first);
+      o << "<" << trace[k].first << (loc.empty() ? "" : " " + loc) << ">";
     }
     o << "\n";
-    o << r.trace[k].second << "\n\n";
+    o << trace[k].second << "\n\n";
   }
   return o.str();
 }
+std::string trace_text(const mc_ctx* c, const rmc::RunResult& r) { return trace_text(c, r.trace); }
 }  // namespace
 
 extern "C" {
@@ -205,6 +207,7 @@ int mc_set_checkpoint(mc_ctx* c, const char* path, int32_t every_levels) {
   if (!c || every_levels < 0) return MC_E_INVALID;
   if (!c->be) return MC_E_STATE;
   if (path && c->ro.sim_walks > 0) { c->last_error = "simulation mode keeps no BFS state: no checkpoints"; return MC_E_UNSUPPORTED; }
+  if (path && c->ro.continue_mode) { c->last_error = "continue mode: no checkpoints"; return MC_E_UNSUPPORTED; }
   if (path && c->ro.count_final_level) {   // a checkpoint must hold every level it names
     c->last_error = "checkpoints store every level: not with count_final_level";
     return MC_E_UNSUPPORTED;
@@ -218,6 +221,7 @@ int mc_set_recover(mc_ctx* c, const char* path) {
   if (!c) return MC_E_INVALID;
   if (!c->be) return MC_E_STATE;
   if (path && c->ro.sim_walks > 0) { c->last_error = "simulation mode starts every walk from Init: nothing to recover"; return MC_E_UNSUPPORTED; }
+  if (path && c->ro.continue_mode) { c->last_error = "continue mode starts from Init: nothing to recover"; return MC_E_UNSUPPORTED; }
   c->ro.recover_path = path ? path : "";
   return MC_OK;
 }
@@ -344,6 +348,13 @@ int mc_run(mc_ctx* c) {
   if (c->ro.sim_walks > 0) {   // mc_set_simulate checked these; they cannot have changed since
     if (c->n_gpus > 1 || !c->be->supports_simulation()) { c->ran = false; c->last_error = "simulation mode: one GPU, raft_original only"; return MC_E_UNSUPPORTED; }
   }
+  if (c->ro.continue_mode) {   // mc_set_continue checked these; refused again rather than run as a plain search
+    if (c->n_gpus > 1 || !c->be->supports_continue() || c->ro.sim_walks > 0 || !c->ro.checkpoint_path.empty() || !c->ro.recover_path.empty()) {
+      c->ran = false;
+      c->last_error = "continue mode: tlc_membership (hand-compiled) on one GPU, without checkpoint, recover or simulation";
+      return MC_E_UNSUPPORTED;
+    }
+  }
   if (c->n_gpus > 1) { c->ran = false; return run_multi(c); }
   std::string err;
   int rc = c->be->run(c->ro, c->res, err);
@@ -415,7 +426,14 @@ int mc_report(const mc_ctx* c, char** text, size_t* len) {
   const auto& r = c->res;
   std::ostringstream o;
   o << "raftmc (MI355X/gfx950) checking " << c->tla_path << " with " << c->cfg_path << "\n";
-  if (r.verdict == MC_VERDICT_INVARIANT_VIOLATION) {
+  // continue mode: one block per witness, in discovery order (the first is the run's counterexample)
+  for (const auto& w : r.witnesses) {
+    o << "Error: Invariant " << w.invariant << " is violated.\n";
+    o << "Error: The behavior up to this point is:\n" << trace_text(c, w.trace);
+  }
+  if (r.verdict == MC_VERDICT_INVARIANT_VIOLATION && r.continued) {
+    // (the blocks above)
+  } else if (r.verdict == MC_VERDICT_INVARIANT_VIOLATION) {
     o << "Error: Invariant " << r.violated << " is violated.\n";
     o << "Error: The behavior up to this point is:\n" << trace_text(c, r);
   } else if (r.verdict == MC_VERDICT_DEADLOCK) {
@@ -542,6 +560,10 @@ int mc_exit_code(const mc_ctx* c) {
   } \
   if (c->ro.sim_walks > 0) { \
     c->last_error = "simulation mode runs on one GPU (mc_run); a sharded run cannot use it"; \
+    return MC_E_UNSUPPORTED; \
+  } \
+  if (c->ro.continue_mode) { \
+    c->last_error = "continue mode runs on one GPU (mc_run); a sharded run cannot use it"; \
     return MC_E_UNSUPPORTED; \
   }
 #define SHARD_RC(expr)                      \
@@ -689,6 +711,10 @@ int mc_shard_run_loopback(mc_ctx* const* ctxs, int32_t world) {
       ctxs[r]->last_error = "simulation mode runs on one GPU (mc_run); a sharded run cannot use it";
       return MC_E_UNSUPPORTED;
     }
+    if (ctxs[r]->ro.continue_mode) {
+      ctxs[r]->last_error = "continue mode runs on one GPU (mc_run); a sharded run cannot use it";
+      return MC_E_UNSUPPORTED;
+    }
   }
   rmc::LoopbackWorld w(world);
   std::vector<int> rcs(world, MC_OK);
@@ -726,6 +752,7 @@ int mc_set_simulate(mc_ctx* c, int64_t num_walks, int64_t batch) {
   if (!c->ro.checkpoint_path.empty() || !c->ro.recover_path.empty()) return refuse("simulation mode: not with a checkpoint or recover path");
   if (c->n_gpus > 1) return refuse("simulation mode runs on one GPU (n_gpus = 1)");
   if (c->ro.count_final_level) return refuse("simulation mode: not with count_final_level");
+  if (c->ro.continue_mode) return refuse("simulation mode: not with continue mode");
   c->ro.sim_walks = num_walks; c->ro.sim_batch = batch;
   return MC_OK;
 }
@@ -747,6 +774,48 @@ int mc_sim_walk(mc_ctx* c, int64_t walk, char** text, size_t* len) {
   if (rc) { c->last_error = err; return rc; }
   *text = dup_text(t, len);
   return *text ? MC_OK : MC_E_OOM;
+}
+
+// ------------------------------------------------------------------ continue mode
+int mc_set_continue(mc_ctx* c, int32_t on) {
+  if (!c) return MC_E_INVALID;
+  if (!c->be) return MC_E_STATE;
+  if (!on) { c->ro.continue_mode = false; return MC_OK; }
+  auto refuse = [&](const char* why) { c->last_error = why; return MC_E_UNSUPPORTED; };
+  if (!c->be->supports_continue())
+    return refuse("continue mode (-continue) exists for tlc_membership/raft.tla (hand-compiled) only; this spec is not run as a plain "
+                  "search instead");
+  if (c->n_gpus > 1) return refuse("continue mode runs on one GPU (n_gpus = 1)");
+  if (!c->ro.checkpoint_path.empty() || !c->ro.recover_path.empty()) return refuse("continue mode: not with a checkpoint or recover path");
+  if (c->ro.sim_walks > 0) return refuse("continue mode: not with simulation");
+  c->ro.continue_mode = true;
+  return MC_OK;
+}
+
+int mc_witness_count(const mc_ctx* c, int32_t* n) {
+  if (!c || !n) return MC_E_INVALID;
+  if (!c->ran || !c->res.continued) return MC_E_STATE;
+  *n = (int32_t)c->res.witnesses.size();
+  return MC_OK;
+}
+
+int mc_witness(const mc_ctx* c, int32_t k, mc_witness_t* out, char** trace, size_t* len) {
+  if (!c || !out) return MC_E_INVALID;
+  if (!c->ran || !c->res.continued) return MC_E_STATE;
+  if (k < 0 || k >= (int32_t)c->res.witnesses.size()) return MC_E_INVALID;
+  const rmc::Witness& w = c->res.witnesses[k];
+  std::memset(out, 0, sizeof *out);
+  std::snprintf(out->invariant, sizeof out->invariant, "%s", w.invariant.c_str());
+  out->position = w.position;
+  out->depth = w.depth; out->generated = w.generated; out->distinct = w.distinct; out->left_on_queue = w.left_on_queue;
+  const size_t na = std::min<size_t>(w.act_generated.size(), 32);
+  out->n_actions = (int32_t)na;
+  for (size_t a = 0; a < na; ++a) { out->act_generated[a] = w.act_generated[a]; out->act_distinct[a] = w.act_distinct[a]; }
+  if (trace) {
+    *trace = dup_text(trace_text(c, w.trace), len);
+    if (!*trace) return MC_E_OOM;
+  }
+  return MC_OK;
 }
 
 #ifndef RAFTMC_SOURCE_HASH

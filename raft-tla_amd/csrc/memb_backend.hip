@@ -864,6 +864,8 @@ __global__ void __launch_bounds__(BS) memb_unpack_states(const u32* in, u64 n, u
   meta[first + i] = (u64)in[i * RW + NWP] | ((u64)in[i * RW + NWP + 1] << 32);
 }
 
+#include "memb_witness.hip"   // continue mode: the per-invariant witness kernels
+
 #define HIPCHK(x)                                                                             \
   do {                                                                                        \
     hipError_t e_ = (x);                                                                      \
@@ -927,6 +929,7 @@ class MembGpu : public Backend {
   }
 
   std::string family() const override { return "tlc_membership"; }
+  bool supports_continue() const override { return true; }
 
   int observed_collision(double& v, std::string& err) override {
     if (!d_table_ || sharded_) { err = "after a single-GPU mc_run only"; return MC_E_STATE; }
@@ -1000,6 +1003,11 @@ class MembGpu : public Backend {
 
   int run(const RunOpts& o, RunResult& r, std::string& err) override {
     sharded_ = false;
+    const bool cont = o.continue_mode;
+    if (cont && (!o.checkpoint_path.empty() || !o.recover_path.empty() || o.sim_walks > 0)) {
+      err = "continue mode: not with a checkpoint or recover path, nor with simulation";
+      return MC_E_UNSUPPORTED;
+    }
     for (int q = 0; q < 2; ++q)
       if (((m_.rt.constraints >> kPrefixCon[q]) & 1u) && !have_prefix_[q]) {
         err = std::string(kMembConNames[kPrefixCon[q]]) + " needs its golden history trace: place the reference's "
@@ -1025,6 +1033,38 @@ class MembGpu : public Backend {
     base_ = 0; host_.clear();
     u64 level_begin = 0, level_count = 1;
     u32 level = 0;
+    // continue mode: the BFS kernels get a runtime without invariants, the witness
+    // kernels (memb_witness.hip) the cfg positions still pending; wits in discovery order
+    MembRuntime rt_bfs = rt_dev_;
+    u32 pending = 0;
+    std::vector<Witness> wits;
+    RunResult last_wit;                   // the result as of the last witness's stop point
+    if (cont) {
+      rt_bfs.n_inv = 0;
+      pending = rt.n_inv >= 32 ? ~0u : (1u << rt.n_inv) - 1u;
+      r.continued = true;
+      r.kernels.push_back({"memb_witness", 0, 0, 0});
+      if (!d_wit_) HIPCHK(hipMalloc(&d_wit_, WIT_N * 8));
+      for (auto& e : ev_w_) if (!e) HIPCHK(hipEventCreate(&e));
+    }
+    auto add_witness = [&](const RunResult& at, u32 q) {
+      Witness w;
+      w.invariant = kMembInvNames[inv_id_at(q)]; w.position = (int)q;
+      w.depth = at.depth; w.generated = at.generated; w.distinct = at.distinct; w.left_on_queue = at.left_on_queue;
+      w.act_generated = at.act_generated; w.act_distinct = at.act_distinct; w.trace = at.trace;
+      wits.push_back(std::move(w));
+      pending &= ~(1u << q);
+    };
+    // the end of a continue run that has witnesses and no fatal event: the first witness is the
+    // run's counterexample (what the plain run reports)
+    auto finish_continue = [&]() {
+      if (cont && !wits.empty() && (r.verdict == MC_VERDICT_OK || r.verdict == MC_VERDICT_DEPTH_LIMIT)) {
+        r.verdict = MC_VERDICT_INVARIANT_VIOLATION;
+        r.violated = wits[0].invariant;
+        r.trace = wits[0].trace;
+      }
+      r.witnesses = std::move(wits);
+    };
 
     if (!o.recover_path.empty()) {   // TLC -recover: continue the BFS saved by a checkpoint
       if (int rc = load_checkpoint(o.recover_path, r, level_begin, level_count, err)) return rc;
@@ -1046,7 +1086,22 @@ class MembGpu : public Backend {
       const u64 nometa = ~0ull;
       HIPCHK(hipMemcpy(d_meta_, &nometa, 8, hipMemcpyHostToDevice));
       total_ = 1; r.distinct = 1;
-      if (u32 bad = S::check_invariants(s0, rt)) {
+      if (cont) {   // every pending invariant on Init: a violation is a witness of depth 1, the search goes on
+        for (u32 q = 0; q < rt.n_inv; ++q) {
+          const int iv = S::inv(s0, inv_id_at(q), rt);
+          if (iv == IV_ERR) {
+            r.verdict = MC_VERDICT_EVAL_ERROR; r.error = std::string("TLC evaluation error in invariant ") + kMembInvNames[inv_id_at(q)];
+            r.trace.push_back({"<Initial predicate>", text_.text(s0, true)});
+            finish_continue(); finish(r, t0); return 0;
+          }
+          if (iv == IV_BAD) {
+            RunResult at = r;
+            at.trace.push_back({"<Initial predicate>", text_.text(s0, true)});
+            add_witness(at, q);
+          }
+        }
+        if (!wits.empty() && !pending) { finish_continue(); finish(r, t0); return 0; }
+      } else if (u32 bad = S::check_invariants(s0, rt)) {
         if ((bad >> 8) == IV_BAD) { r.verdict = MC_VERDICT_INVARIANT_VIOLATION; r.violated = kMembInvNames[bad & 255]; }
         else { r.verdict = MC_VERDICT_EVAL_ERROR; r.error = std::string("TLC evaluation error in invariant ") + kMembInvNames[bad & 255]; }
         r.trace.push_back({"<Initial predicate>", text_.text(s0, true)});
@@ -1088,7 +1143,7 @@ class MembGpu : public Backend {
         MGenArgs g;
         g.states = sp; g.chunk_begin = cb; g.chunk_count = cnt; g.rank0 = rank0; g.cand = d_cand_; g.cells = d_cells_;
         g.cells_oom = d_cells_oom_; g.cell_count = d_cell_count_; g.nsucc = d_nsucc_;
-        g.seed = r.seed; g.rt = rt_dev_; g.inv_oom = o.inv_out_of_model ? 1u : 0u; g.deadlock = o.check_deadlock ? 1u : 0u; g.ctr = (unsigned long long*)d_ctr_;
+        g.seed = r.seed; g.rt = rt_bfs; g.inv_oom = o.inv_out_of_model ? 1u : 0u; g.deadlock = o.check_deadlock ? 1u : 0u; g.ctr = (unsigned long long*)d_ctr_;
         g.smask = d_smask_;
         MDedupArgs d;
         d.cells = d_cells_; d.cell_count = d_cell_count_;
@@ -1106,7 +1161,8 @@ class MembGpu : public Backend {
         hipLaunchKernelGGL((memb_expand<S>), dim3(nblk), dim3(BS), 0, stream_, g);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(ev_[8], stream_));
-        if (o.inv_out_of_model) hipLaunchKernelGGL((memb_oom_check<S>), dim3(nblk), dim3(BS), 0, stream_, g);
+        // (continue mode: memb_witness_oom takes this launch's place, after memb_materialize)
+        if (o.inv_out_of_model && !cont) hipLaunchKernelGGL((memb_oom_check<S>), dim3(nblk), dim3(BS), 0, stream_, g);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(ev_[0], stream_));
         if (int rc = launch_fingerprint(g, nblk, err)) return rc;
@@ -1131,7 +1187,7 @@ class MembGpu : public Backend {
         if (nnew && next_write + nnew <= cap_end) {
           MMatArgs m;
           m.states = sp; m.meta = mp; m.newrec = d_newrec_; m.n_new = nnew; m.dst_base = next_write; m.cap = cap_end;
-          m.level_begin = level_begin; m.gid_tag = 0; m.rt = rt_dev_; m.ctr = (unsigned long long*)d_ctr_;
+          m.level_begin = level_begin; m.gid_tag = 0; m.rt = rt_bfs; m.ctr = (unsigned long long*)d_ctr_;
           HIPCHK(hipEventRecord(ev_[5], stream_));
           if (rt_dev_.sym_tlc) hipLaunchKernelGGL((memb_materialize<S, true>), dim3((unsigned)((nnew + BS - 1) / BS)), dim3(BS), 0, stream_, m);
           else hipLaunchKernelGGL((memb_materialize<S, false>), dim3((unsigned)((nnew + BS - 1) / BS)), dim3(BS), 0, stream_, m);
@@ -1152,9 +1208,72 @@ class MembGpu : public Backend {
         r.kernels[4].ms += ms_c; r.kernels[4].launches++; r.kernels[4].algo_bytes += (double)nslots * 8 + (double)nnew * 8;
         if (ms_m > 0) { r.kernels[5].ms += ms_m; r.kernels[5].launches++; r.kernels[5].algo_bytes += (double)nnew * (8 + 2 * S_B + 8); }
         if (next_write + nnew > cap_end) { c[C_ERR] |= MERR_STORE; stop = true; }
+        u32 fatal_pending = 0;
+        if (cont && !c[C_ERR]) {
+          // This chunk's witnesses: per pending position the minimum violating key, unless a fatal event
+          // (an invariant that failed to evaluate, a next-state error, a deadlock) comes first in key
+          // order.  The kernels evaluate a position on the whole chunk, the rules retire it at its
+          // witness: when an invariant's error is the fatal event and positions were retired before
+          // it, the pass runs again without them (the error may have been one of theirs).
+          const bool wnew = nnew && next_write + nnew <= cap_end;   // (memb_materialize ran: the chunk's new states are stored)
+          std::vector<std::pair<u64, u32>> hits;
+          u32 mask = pending;
+          u64 fatal = c[C_EVENT];
+          while (mask && (o.inv_out_of_model || wnew)) {
+            MWitArgs wa;
+            wa.states = sp; wa.meta = mp; wa.first = next_write; wa.n_new = nnew; wa.level_begin = level_begin; wa.rt = rt_dev_;
+            wa.pending = mask; wa.wit = (unsigned long long*)d_wit_;
+            u64 wit[WIT_N];
+            HIPCHK(hipMemsetAsync(d_wit_, 0xFF, WIT_N * 8, stream_));
+            HIPCHK(hipEventRecord(ev_w_[0], stream_));
+            if (o.inv_out_of_model) hipLaunchKernelGGL((memb_witness_oom<S>), dim3(nblk), dim3(BS), 0, stream_, g, wa);
+            HIPCHK(hipGetLastError());
+            if (wnew) hipLaunchKernelGGL((memb_witness_new<S>), dim3((unsigned)((nnew + BS - 1) / BS)), dim3(BS), 0, stream_, wa);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipEventRecord(ev_w_[1], stream_));
+            HIPCHK(hipMemcpyAsync(wit, d_wit_, sizeof wit, hipMemcpyDeviceToHost, stream_));
+            HIPCHK(hipStreamSynchronize(stream_));
+            float ms_w = 0;
+            (void)hipEventElapsedTime(&ms_w, ev_w_[0], ev_w_[1]);
+            level_ms += ms_w;
+            auto& kw = r.kernels.back();
+            kw.ms += ms_w; kw.launches += (o.inv_out_of_model ? 1 : 0) + (wnew ? 1 : 0);
+            kw.algo_bytes += (double)(wnew ? nnew : 0) * (8 + S::BAGW * 4);
+            fatal = std::min(c[C_EVENT], wit[WIT_FATAL]);
+            u32 found = 0;
+            for (u32 q = 0; q < 32; ++q)
+              if (((mask >> q) & 1u) && wit[q] != ~0ull && ((wit[q] << 2) | EV_VIOLATION) < fatal) { hits.push_back({wit[q], q}); found |= 1u << q; }
+            mask &= ~found;
+            if (!(found && wit[WIT_FATAL] != ~0ull && wit[WIT_FATAL] <= c[C_EVENT])) break;
+            fatal = c[C_EVENT];   // (what holds if the next pass finds no error)
+          }
+          std::sort(hits.begin(), hits.end());
+          fatal_pending = mask;   // an erroring invariant is named among the positions pending at its key
+          // each witness gets TLC's stop point as if the search had ended on it, on a copy of the result
+          for (const auto& h : hits) {
+            u64 c2[C_NCTR];
+            std::memcpy(c2, c, sizeof c2);
+            c2[C_EVENT] = (h.first << 2) | EV_VIOLATION;
+            RunResult at = r;
+            handle_event(c2, cnt, level_begin, level_count, rank0, gen_before_chunk, next_write - (level_begin + level_count), nnew, level, at,
+                         (int)h.second);
+            stop_action_counts(c2, sp, mp, cb, level_begin, rank0, next_write, act_before_chunk, at);
+            add_witness(at, h.second);
+            last_wit = std::move(at);
+          }
+          c[C_EVENT] = fatal;
+          if (fatal == ~0ull && !pending && !hits.empty()) {
+            // every listed invariant has its witness: the run ends at the last one's stop point
+            r.generated = last_wit.generated; r.distinct = last_wit.distinct; r.left_on_queue = last_wit.left_on_queue;
+            r.depth = last_wit.depth; r.act_generated = last_wit.act_generated; r.act_distinct = last_wit.act_distinct;
+            r.verdict = MC_VERDICT_INVARIANT_VIOLATION;
+            stop = true;
+          }
+        }
         if (c[C_EVENT] != ~0ull) {
           // first event of this chunk in key order (earlier chunks had none)
-          handle_event(c, cnt, level_begin, level_count, rank0, gen_before_chunk, next_write - (level_begin + level_count), nnew, level, r);
+          handle_event(c, cnt, level_begin, level_count, rank0, gen_before_chunk, next_write - (level_begin + level_count), nnew, level, r,
+                       -1, fatal_pending);
           stop_action_counts(c, sp, mp, cb, level_begin, rank0, next_write, act_before_chunk, r);
           stop = true;
         }
@@ -1180,6 +1299,7 @@ class MembGpu : public Backend {
       }
       if (stop) {
         if (r.verdict == MC_VERDICT_OK) r.verdict = MC_VERDICT_CAPACITY_OVERFLOW;
+        if (r.verdict == MC_VERDICT_INVARIANT_VIOLATION && cont) { r.violated = wits[0].invariant; r.trace = wits[0].trace; }
         break;
       }
       int64_t gen = 0;
@@ -1200,6 +1320,7 @@ class MembGpu : public Backend {
       if (o.checkpoint_every > 0 && !o.checkpoint_path.empty() && r.depth % o.checkpoint_every == 0 && level_count > 0)
         if (int rc = save_checkpoint(o.checkpoint_path, r, level_begin, level_count, err)) return rc;
     }
+    finish_continue();
     finish(r, t0);
     return 0;
   }
@@ -1349,7 +1470,9 @@ class MembGpu : public Backend {
 
   // The first event of the level: reproduce TLC's (the oracle's) stop point, counts and trace.
   void handle_event(const u64* c, u64 cnt, u64 level_begin, u64 level_count, u64 rank0, int64_t gen_before_chunk,
-                    u64 new_before_chunk, u64 nnew, u32 level, RunResult& r) {
+                    u64 new_before_chunk, u64 nnew, u32 level, RunResult& r, int pos = -1, u32 pending = 0) {
+    // continue mode: pos >= 0 names a violation's invariant by its cfg position; pending != 0 names an
+    // erroring invariant among those positions (the plain run: check_invariants' first hit)
     const u64 ev = c[C_EVENT], key = ev >> 2;
     const int kind = (int)(ev & 3);
     const u64 rank = key / S::NSLOT, slot = key % S::NSLOT, gid = level_begin + rank;
@@ -1392,7 +1515,11 @@ class MembGpu : public Backend {
     W t; u32 e2 = 0;
     const int act = S::apply(s, k, sub, t, e2, rt_host_);
     const u32 res = S::check_invariants(t, rt_host_);
-    const int id = (int)(res & 255);
+    int id = (int)(res & 255);
+    if (pos >= 0) id = inv_id_at((u32)pos);
+    else if (pending && kind == EV_INV_ERROR)
+      for (u32 q = 0; q < rt_host_.n_inv; ++q)
+        if (((pending >> q) & 1u) && S::inv(t, inv_id_at(q), rt_host_) == IV_ERR) { id = inv_id_at(q); break; }
     if (kind == EV_INV_ERROR) {
       r.verdict = MC_VERDICT_EVAL_ERROR;
       r.error = std::string("Evaluating invariant ") + kMembInvNames[id] +
@@ -1866,6 +1993,9 @@ class MembGpu : public Backend {
   u64* d_cand_ = nullptr; u64* d_newrec_ = nullptr; unsigned short* d_nsucc_ = nullptr; unsigned int* d_woff_ = nullptr;
   u32* d_cells_ = nullptr; u32* d_cells_oom_ = nullptr; u32* d_cell_count_ = nullptr; u32* d_big_ = nullptr;
   u64* d_smask_ = nullptr;   // [SMW][chunk] in-model slot masks (single-GPU loop)
+  u64* d_wit_ = nullptr;     // continue mode: the chunk's witness words (memb_witness.hip), allocated by its first run
+  hipEvent_t ev_w_[2] = {};  // ... and memb_witness_new's timing events
+  int inv_id_at(u32 q) const { return (int)((rt_host_.inv_order[q / 8] >> (8 * (q % 8))) & 255u); }   // cfg position -> MembInv
   static constexpr int SMW = (S::NSLOT + 63) / 64;
   int fp_slice_test_ = -1;   // RunOpts::test_fp_slice of the current run
   u64* d_bsum_ = nullptr;
@@ -1947,6 +2077,8 @@ class MembGpu : public Backend {
                     (void*)d_nsucc_, (void*)d_woff_, (void*)d_bsum_, (void*)d_cells_, (void*)d_cells_oom_, (void*)d_cell_count_, (void*)d_big_, (void*)d_smask_})
       if (p) (void)hipFree(p);
     for (auto& e : ev_) { if (e) (void)hipEventDestroy(e); e = nullptr; }
+    for (auto& e : ev_w_) { if (e) (void)hipEventDestroy(e); e = nullptr; }
+    if (d_wit_) { (void)hipFree(d_wit_); d_wit_ = nullptr; }
     if (stream_) (void)hipStreamDestroy(stream_);
     d_table_ = nullptr; d_states_ = nullptr; d_meta_ = nullptr; d_ctr_ = nullptr; d_cand_ = nullptr; d_newrec_ = nullptr;
     d_nsucc_ = nullptr; d_woff_ = nullptr; d_bsum_ = nullptr; d_cells_ = nullptr; d_cells_oom_ = nullptr; d_cell_count_ = nullptr; d_big_ = nullptr; d_smask_ = nullptr; stream_ = nullptr;

@@ -2,7 +2,9 @@
 //   raftmc [-config F.cfg] [-workers N] [-deadlock] [-depth D] [-device K]
 //          [-fptable BYTES] [-store BYTES] [-seed S] [-no-inv-oom] [-no-disjunct-copies] [-dump FILE] [-json]
 //          [-checkpoint LEVELS] [-checkpoint-file FILE] [-recover FILE] [-symmetry tlc|orbit]
-//          [-gpus N] [-countfinal] [-simulate [num=N]] F.tla
+//          [-gpus N] [-countfinal] [-simulate [num=N]] [-continue] F.tla
+// (-continue, tlc_membership: one search reports the first counterexample of every listed invariant --
+// raftmc's own semantics, not TLC's -continue, which prints every violating state; mc_set_continue)
 // (-simulate [num=N]: TLC's simulation mode for raft_original -- N seeded random walks of at most
 // -depth states (default 100) with -seed S, invariants checked along each walk.  Without num= TLC
 // runs until interrupted; raftmc runs one batch, 262144 walks.  -aril is not supported.)
@@ -27,7 +29,7 @@ int main(int argc, char** argv) {
   mc_default_opts(&o);
   std::string tla, cfg, dump, ckpt_file = "states/raftmc.ckpt", recover;
   int ckpt_every = 0;
-  bool json = false, simulate = false;
+  bool json = false, simulate = false, cont = false;
   long long sim_num = 262144;   // -simulate without num=: one batch
   for (int a = 1; a < argc; ++a) {
     std::string k = argv[a];
@@ -64,6 +66,7 @@ int main(int argc, char** argv) {
         if (sim_num <= 0) { std::fprintf(stderr, "-simulate num=N needs N > 0\n"); return 2; }
       }
     }
+    else if (k == "-continue") cont = true;
     else if (k == "-aril") { std::fprintf(stderr, "-aril is not supported: the walks' random numbers are counter-based (-seed)\n"); return 2; }
     else if (k == "-dump") dump = val();
     else if (k == "-json") json = true;
@@ -76,7 +79,8 @@ int main(int argc, char** argv) {
   if (tla.empty()) {
     std::fprintf(stderr, "usage: raftmc [-config F.cfg] [options] F.tla\n"
                          "  -simulate [num=N]  N random walks of at most -depth states (default 100), seeded by -seed;\n"
-                         "                     without num= one batch of 262144 walks (TLC: until interrupted)\n");
+                         "                     without num= one batch of 262144 walks (TLC: until interrupted)\n"
+                         "  -continue          tlc_membership: the first counterexample of every listed invariant from one search\n");
     return 2;
   }
   if (cfg.empty()) { cfg = tla.substr(0, tla.size() > 4 ? tla.size() - 4 : tla.size()) + ".cfg"; }
@@ -89,6 +93,7 @@ int main(int argc, char** argv) {
   }
   if (!rc && !recover.empty()) rc = mc_set_recover(c, recover.c_str());
   if (!rc && simulate) rc = mc_set_simulate(c, sim_num, 0);
+  if (!rc && cont) rc = mc_set_continue(c, 1);
   if (rc) { std::fprintf(stderr, "raftmc: %s (code %d)\n", mc_last_error(c), rc); mc_close(c); return 75; }
   rc = mc_run(c);
   if (rc == 0) {   // TLC prints its fingerprint-based estimate after a completed search
@@ -110,8 +115,20 @@ int main(int argc, char** argv) {
                 (long long)sim_walks, (long long)sim_steps, (long long)sim_event);
   } else if (json) {
     mc_summary_t s; mc_summary(c, &s);
-    std::printf("{\"verdict\": %d, \"generated\": %lld, \"distinct\": %lld, \"depth\": %lld, \"seconds\": %.6f, \"kernel_seconds\": %.6f}\n",
+    std::printf("{\"verdict\": %d, \"generated\": %lld, \"distinct\": %lld, \"depth\": %lld, \"seconds\": %.6f, \"kernel_seconds\": %.6f",
                 s.verdict, (long long)s.generated, (long long)s.distinct, (long long)s.depth, s.seconds_total, s.seconds_kernels);
+    int32_t nw = 0;
+    if (cont && mc_witness_count(c, &nw) == 0) {   // continue mode: the witnesses in discovery order
+      std::printf(", \"witnesses\": [");
+      for (int32_t k = 0; k < nw; ++k) {
+        mc_witness_t w;
+        if (mc_witness(c, k, &w, nullptr, nullptr)) break;
+        std::printf("%s{\"invariant\": \"%s\", \"depth\": %lld, \"generated\": %lld, \"distinct\": %lld}", k ? ", " : "", w.invariant,
+                    (long long)w.depth, (long long)w.generated, (long long)w.distinct);
+      }
+      std::printf("]");
+    }
+    std::printf("}\n");
   }
   if (!dump.empty() && mc_dump_states(c, dump.c_str())) std::fprintf(stderr, "raftmc: dump failed: %s\n", mc_last_error(c));
   int ec = mc_exit_code(c);

@@ -32,7 +32,7 @@ EXPORTS = ["mc_opts_init", "mc_default_opts", "mc_open", "mc_run", "mc_summary",
            "mc_set_history_prefix", "mc_shard_layout", "mc_shard_select", "mc_shard_event_stats",
            "mc_collision_observed", "mc_rccl_unique_id", "mc_shard_run_rccl", "mc_shard_run_loopback",
            "mc_set_checkpoint", "mc_set_recover", "mc_action_location", "mc_source_hash", "mc_set_fault_injection", "mc_release_device_memory", "mc_set_fp_slice",
-           "mc_set_simulate", "mc_sim_stats", "mc_sim_walk"]
+           "mc_set_simulate", "mc_sim_stats", "mc_sim_walk", "mc_set_continue", "mc_witness_count", "mc_witness"]
 
 
 class McOpts(ctypes.Structure):
@@ -53,6 +53,24 @@ class McSummary(ctypes.Structure):
                 ("generated_in_model", ctypes.c_int64), ("state_bytes", ctypes.c_int32), ("n_launches", ctypes.c_int32),
                 ("violated", ctypes.c_char * 64), ("spec", ctypes.c_char * 32), ("seen_set_probes", ctypes.c_int64),
                 ("reserved", ctypes.c_int64 * 8)]
+
+
+class McWitness(ctypes.Structure):
+    _fields_ = [("invariant", ctypes.c_char * 64), ("position", ctypes.c_int32), ("n_actions", ctypes.c_int32),
+                ("depth", ctypes.c_int64), ("generated", ctypes.c_int64), ("distinct", ctypes.c_int64),
+                ("left_on_queue", ctypes.c_int64), ("act_generated", ctypes.c_int64 * 32),
+                ("act_distinct", ctypes.c_int64 * 32), ("reserved", ctypes.c_int64 * 8)]
+
+
+class Witness:
+    """Continue mode: the first counterexample of one listed invariant, with TLC's counters at its
+    stop point (what a plain run listing that invariant reports)."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def __repr__(self):
+        return "Witness(%s, depth=%d, generated=%d, distinct=%d)" % (self.invariant, self.depth, self.generated, self.distinct)
 
 
 class RaftMCError(RuntimeError):
@@ -128,6 +146,9 @@ def load_library(path=LIB_PATH):
     lib.mc_set_simulate.argtypes = [P, ctypes.c_int64, ctypes.c_int64]
     lib.mc_sim_stats.argtypes = [P, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
     lib.mc_sim_walk.argtypes = [P, ctypes.c_int64, ctypes.POINTER(P), ctypes.POINTER(ctypes.c_size_t)]
+    lib.mc_set_continue.argtypes = [P, ctypes.c_int32]
+    lib.mc_witness_count.argtypes = [P, ctypes.POINTER(ctypes.c_int32)]
+    lib.mc_witness.argtypes = [P, ctypes.c_int32, ctypes.POINTER(McWitness), ctypes.POINTER(P), ctypes.POINTER(ctypes.c_size_t)]
     lib.mc_exit_code.argtypes = [P]
     lib.mc_free.argtypes = [P]
     lib.mc_close.argtypes = [P]
@@ -253,6 +274,39 @@ class ModelChecker:
         import json
         return json.loads(self._text(self.lib.mc_describe))
 
+    def set_continue(self, on=True):
+        """Continue mode (tlc_membership, one GPU): the next run() reports the first counterexample of
+        every listed invariant from one search (Result.witnesses, in discovery order).  raftmc's own
+        semantics, not TLC's -continue (include/raftmc.h mc_set_continue)."""
+        rc = self.lib.mc_set_continue(self.h, 1 if on else 0)
+        if rc:
+            raise RaftMCError(rc, self.lib.mc_last_error(self.h).decode())
+
+    def witnesses(self):
+        """The witnesses of the last run, in discovery order ([] unless it was a continue run)."""
+        n = ctypes.c_int32()
+        if self.lib.mc_witness_count(self.h, ctypes.byref(n)):
+            return []
+        names = []
+        for k in range(64):
+            name = ctypes.c_char_p()
+            if self.lib.mc_action_stats(self.h, k, ctypes.byref(name), None, None):
+                break
+            names.append(name.value.decode())
+        out = []
+        for k in range(n.value):
+            w, p, ln = McWitness(), ctypes.c_void_p(), ctypes.c_size_t()
+            rc = self.lib.mc_witness(self.h, k, ctypes.byref(w), ctypes.byref(p), ctypes.byref(ln))
+            if rc:
+                raise RaftMCError(rc, self.lib.mc_last_error(self.h).decode())
+            text = ctypes.string_at(p, ln.value).decode()
+            self.lib.mc_free(p)
+            out.append(Witness(invariant=w.invariant.decode(), position=w.position, depth=w.depth, generated=w.generated,
+                               distinct=w.distinct, left_on_queue=w.left_on_queue,
+                               actions={names[a]: [w.act_generated[a], w.act_distinct[a]] for a in range(w.n_actions)},
+                               trace_text=text))
+        return out
+
     def run(self):
         rc = self.lib.mc_run(self.h)
         if rc:
@@ -291,7 +345,7 @@ class ModelChecker:
                       state_bytes=s.state_bytes, n_launches=s.n_launches,
                       trace_text=self._text(self.lib.mc_trace), report=self._text(self.lib.mc_report),
                       error=self.lib.mc_last_error(self.h).decode(),
-                      exit_code=self.lib.mc_exit_code(self.h))
+                      exit_code=self.lib.mc_exit_code(self.h), witnesses=self.witnesses())
 
     def simulate(self, num_walks, batch=0):
         """TLC -simulate (raft_original): `num_walks` seeded random walks of at most max_depth states
@@ -350,6 +404,7 @@ def tlc_main(argv):
     spec, config, kw = None, None, {}
     checkpoint, recover = None, None
     simulate = None
+    cont = False
     argv = list(argv)
     it = iter(argv)
     for a in it:
@@ -363,6 +418,8 @@ def tlc_main(argv):
             simulate = 262144
         elif a.startswith("num=") and simulate is not None:
             simulate = int(a[4:])
+        elif a == "-continue":                   # raftmc: every listed invariant's first counterexample (tlc_membership)
+            cont = True
         elif a == "-seed":
             kw["seed"] = int(next(it), 0)
         elif a == "-aril":
@@ -395,6 +452,8 @@ def tlc_main(argv):
             mc.set_checkpoint(path, checkpoint)
         if recover:
             mc.set_recover(recover)
+        if cont:
+            mc.set_continue(True)
         res = mc.simulate(simulate) if simulate is not None else mc.run()
     print(res.report, end="")
     return res.exit_code
