@@ -3,6 +3,7 @@
 #pragma once
 #include <stdint.h>
 
+#include <chrono>
 #include <string>
 #include <vector>
 
@@ -134,6 +135,25 @@ struct Backend {
   virtual int shard_select(int64_t* reply_counts, std::string& err) { (void)reply_counts; err = "not a FIFO-ranked spec"; return -4; }
   virtual int shard_event_stats(const int64_t* g, int64_t* st, std::string& err) { (void)g; (void)st; err = "not a FIFO-ranked spec"; return -4; }
 };
+
+// the end of every run: TLC's optimistic collision estimate and the wall clock
+inline void finish(RunResult& r, std::chrono::steady_clock::time_point t0) {
+  const double M = (double)r.distinct, Ng = (double)r.generated;
+  r.collision_optimistic = M * (Ng - M) / 18446744073709551616.0;
+  r.seconds_total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// what either family's checkpoint header (ckpt_file.h) keeps of a run, and back; the per-action and
+// per-level counters go to and from the file as they lie in RunResult
+template <class H>
+void ckpt_of_run(const RunResult& r, const std::string& desc, H& h) {
+  h.seed = r.seed; h.generated = r.generated; h.distinct = r.distinct; h.depth = r.depth; h.generated_in_model = r.generated_in_model;
+  h.n_act = (int64_t)r.act_generated.size(); h.n_levels = (int64_t)r.levels.size(); h.desc_len = (int64_t)desc.size();
+}
+template <class H>
+void run_of_ckpt(const H& h, RunResult& r) {
+  r.seed = h.seed; r.generated = h.generated; r.distinct = h.distinct; r.depth = h.depth; r.generated_in_model = h.generated_in_model;
+}
 
 Backend* make_orig_backend(const CfgFile& cfg);   // throws CfgError
 Backend* make_memb_backend(const CfgFile& cfg);   // throws CfgError

@@ -46,10 +46,10 @@
 #include "backend.h"
 #include "fifo_shard_loop.h"
 #include "fp_gap.h"
-#include "host_store.h"
 #include "memb_prefix.h"
 #include "memb_spec.h"
 #include "memb_text.h"
+#include "state_store.h"
 
 namespace rmc {
 
@@ -974,14 +974,13 @@ class MembGpu : public Backend {
     uint64_t slots = 1; while (slots * 2 * 16 <= tb) slots *= 2;
     if (slots < 1024) slots = 1024;
     const uint64_t sb = o.state_store_bytes ? o.state_store_bytes : std::min<uint64_t>(160ull << 30, freeb / 2);
-    cap_ = std::max<u64>(16, sb / (NWP * 4 + 8));
+    const u64 cap = std::max<u64>(16, sb / (NWP * 4 + 8));
     // chunk: cand + newrec hold NSLOT u64 per state; ~1/8 of the store bytes, <= SCAN_MAX_BLOCKS blocks
-    chunk_ = std::max<u64>(BS, std::min<u64>({cap_, (sb / 8) / (16 * (u64)S::NSLOT), (u64)SCAN_MAX_BLOCKS * BS}));
+    chunk_ = std::max<u64>(BS, std::min<u64>({cap, (sb / 8) / (16 * (u64)S::NSLOT), (u64)SCAN_MAX_BLOCKS * BS}));
     chunk_ = (chunk_ / BS) * BS;
     table_mask_ = slots - 1;
     HIPCHK(hipMalloc(&d_table_, slots * 16));
-    HIPCHK(hipMalloc(&d_states_, cap_ * NWP * 4));
-    HIPCHK(hipMalloc(&d_meta_, cap_ * 8));
+    HIPCHK(store_.alloc(cap, NWP));
     HIPCHK(hipMalloc(&d_cand_, chunk_ * S::NSLOT * 8));
     HIPCHK(hipMalloc(&d_newrec_, chunk_ * S::NSLOT * 8));
     HIPCHK(hipMalloc(&d_nsucc_, chunk_ * 2));
@@ -1030,7 +1029,7 @@ class MembGpu : public Backend {
     r.kernels = {{"memb_expand", 0, 0, 0}, {"memb_fingerprint", 0, 0, 0}, {"memb_dedup", 0, 0, 0},
                  {"memb_select", 0, 0, 0}, {"memb_compact", 0, 0, 0}, {"memb_materialize", 0, 0, 0}};
     const MembRuntime& rt = rt_host_;
-    base_ = 0; host_.clear();
+    store_.reset();
     u64 level_begin = 0, level_count = 1;
     u32 level = 0;
     // continue mode: the BFS kernels get a runtime without invariants, the witness
@@ -1074,7 +1073,7 @@ class MembGpu : public Backend {
     W s0; S::init(s0);
     r.generated = 1; r.depth = 1;
     r.levels.push_back({1, 0, 0.0});
-    total_ = 0;
+    store_.set_total(0);
     if (!S::in_model(s0, s0, rt)) { r.distinct = 0; r.depth = 0; finish(r, t0); return 0; }
     {
       u32 w0[S::NW]; S::pack(s0, w0);
@@ -1082,10 +1081,10 @@ class MembGpu : public Backend {
       const u64 fp0 = S::fingerprint(s0, r.seed, rt);
       u64 e2[2] = {fp0, ~0ull};   // level 0, key 0: the stored side value is ~(0 << 40 | 0)
       HIPCHK(hipMemcpy(d_table_ + 2 * (fp0 & table_mask_), e2, 16, hipMemcpyHostToDevice));
-      HIPCHK(hipMemcpy(d_states_, wp, NWP * 4, hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(store_.states(), wp, NWP * 4, hipMemcpyHostToDevice));
       const u64 nometa = ~0ull;
-      HIPCHK(hipMemcpy(d_meta_, &nometa, 8, hipMemcpyHostToDevice));
-      total_ = 1; r.distinct = 1;
+      HIPCHK(hipMemcpy(store_.meta(), &nometa, 8, hipMemcpyHostToDevice));
+      store_.set_total(1); r.distinct = 1;
       if (cont) {   // every pending invariant on Init: a violation is a witness of depth 1, the search goes on
         for (u32 q = 0; q < rt.n_inv; ++q) {
           const int iv = S::inv(s0, inv_id_at(q), rt);
@@ -1116,16 +1115,16 @@ class MembGpu : public Backend {
       // the device keeps what the search still reads (the frontier) and writes (the next level);
       // when the next level, predicted from the last growth ratio with a 1.5x margin, might not
       // fit behind what is stored, the completed levels move to host memory
-      if (level_begin > base_) {
+      if (level_begin > store_.base()) {
         const double prev = r.levels.size() >= 2 ? (double)r.levels[r.levels.size() - 2].states : 1.0;
         const double pred = (double)level_count * std::max(1.0, (double)level_count / std::max(prev, 1.0)) * 1.5;
-        if ((double)(total_ - base_) + pred > (double)cap_)
-          if (int rc = spill(level_begin, level_count, err)) return rc;
+        if ((double)(store_.total() - store_.base()) + pred > (double)store_.cap())
+          if (int rc = store_.spill(level_begin, level_count, stream_, false, err)) return rc;
       }
-      // kernels index the store by global id: the device part holds [base_, base_ + cap_)
-      u32* const sp = d_states_ - base_ * NWP;
-      u64* const mp = d_meta_ - base_;
-      const u64 cap_end = base_ + cap_;
+      // kernels index the store by global id: the device part holds [base, base + cap)
+      u32* const sp = store_.states() - store_.base() * NWP;
+      u64* const mp = store_.meta() - store_.base();
+      const u64 cap_end = store_.base() + store_.cap();
       HIPCHK(hipMemsetAsync(d_ctr_, 0, C_NCTR * 8, stream_));
       HIPCHK(hipMemsetAsync(d_ctr_ + C_EVENT, 0xFF, 8, stream_));
       u64 next_write = level_begin + level_count;
@@ -1255,8 +1254,8 @@ class MembGpu : public Backend {
             std::memcpy(c2, c, sizeof c2);
             c2[C_EVENT] = (h.first << 2) | EV_VIOLATION;
             RunResult at = r;
-            handle_event(c2, cnt, level_begin, level_count, rank0, gen_before_chunk, next_write - (level_begin + level_count), nnew, level, at,
-                         (int)h.second);
+            if (int rc = handle_event(c2, cnt, level_begin, level_count, rank0, gen_before_chunk, next_write - (level_begin + level_count), nnew, level,
+                                      at, err, (int)h.second)) return rc;
             stop_action_counts(c2, sp, mp, cb, level_begin, rank0, next_write, act_before_chunk, at);
             add_witness(at, h.second);
             last_wit = std::move(at);
@@ -1272,8 +1271,8 @@ class MembGpu : public Backend {
         }
         if (c[C_EVENT] != ~0ull) {
           // first event of this chunk in key order (earlier chunks had none)
-          handle_event(c, cnt, level_begin, level_count, rank0, gen_before_chunk, next_write - (level_begin + level_count), nnew, level, r,
-                       -1, fatal_pending);
+          if (int rc = handle_event(c, cnt, level_begin, level_count, rank0, gen_before_chunk, next_write - (level_begin + level_count), nnew, level,
+                                    r, err, -1, fatal_pending)) return rc;
           stop_action_counts(c, sp, mp, cb, level_begin, rank0, next_write, act_before_chunk, r);
           stop = true;
         }
@@ -1309,8 +1308,8 @@ class MembGpu : public Backend {
       r.generated_in_model += (int64_t)gen_in_level;
       const u64 nnew = next_write - (level_begin + level_count);
       r.algo_bytes += (double)level_count * S_B + (double)gen_in_level * 8 + (double)nnew * (16 + S_B);
-      total_ = next_write;
-      r.distinct = (int64_t)total_;
+      store_.set_total(next_write);
+      r.distinct = (int64_t)next_write;
       r.levels.back().generated = gen;
       r.levels.back().kernel_ms = level_ms;
       if (nnew > 0) { r.levels.push_back({(int64_t)nnew, 0, 0.0}); r.depth += 1; }
@@ -1326,151 +1325,42 @@ class MembGpu : public Backend {
   }
 
   // ---------------------------------------------------------------- checkpoint / recover
-  // TLC -checkpoint / -recover (its states/ directory, reference .gitignore:3).  File: magic, the
-  // model's describe_json and symmetry mode (a checkpoint only resumes the same model), the BFS
-  // position and TLC's counters, then the stored states [0, total) and their parent pointers.
-  // Written straight from the host part and, in bounded blocks, from the device part (no second
-  // copy of the store in host memory).  The seen-set is rebuilt from the states on recovery.
-  struct CkptHead {
-    char magic[8];
-    u64 nwp, total, level_begin, level_count, seed, sym_tlc;
-    int64_t generated, distinct, depth, generated_in_model, n_act, n_levels, desc_len;
-  };
-  static constexpr u64 kCkptBlock = 1u << 20;   // states per device<->file block
+  // TLC -checkpoint / -recover (its states/ directory, reference .gitignore:3): ckpt::MembHead
+  // around the shared framing (ckpt_file.h) and store body (state_store.h)
   int save_checkpoint(const std::string& path, const RunResult& r, u64 level_begin, u64 level_count, std::string& err) {
     const std::string desc = describe_json();
-    CkptHead h;
+    ckpt::MembHead h;
     std::memcpy(h.magic, "RAFTMCM1", 8);
-    h.nwp = NWP; h.total = total_; h.level_begin = level_begin; h.level_count = level_count; h.seed = r.seed;
     h.sym_tlc = rt_host_.sym_tlc;
-    h.generated = r.generated; h.distinct = r.distinct; h.depth = r.depth; h.generated_in_model = r.generated_in_model;
-    h.n_act = MA_NACT; h.n_levels = (int64_t)r.levels.size(); h.desc_len = (int64_t)desc.size();
-    const std::string tmp = path + ".tmp";
-    FILE* f = std::fopen(tmp.c_str(), "wb");
-    if (!f) { err = "cannot write checkpoint " + tmp; return MC_E_IO; }
-    bool ok = std::fwrite(&h, sizeof h, 1, f) == 1 && std::fwrite(desc.data(), 1, desc.size(), f) == desc.size() &&
-              std::fwrite(r.act_generated.data(), 8, MA_NACT, f) == (size_t)MA_NACT &&
-              std::fwrite(r.act_distinct.data(), 8, MA_NACT, f) == (size_t)MA_NACT;
-    for (const auto& lv : r.levels) ok = ok && std::fwrite(&lv.states, 8, 1, f) == 1 && std::fwrite(&lv.generated, 8, 1, f) == 1;
-    ok = ok && host_.write_states(f);
-    std::vector<u32> blk;
-    for (u64 b = base_; ok && b < total_; b += kCkptBlock) {
-      const u64 n = std::min<u64>(kCkptBlock, total_ - b);
-      blk.resize(n * NWP);
-      ok = hipMemcpy(blk.data(), d_states_ + (b - base_) * NWP, n * NWP * 4, hipMemcpyDeviceToHost) == hipSuccess &&
-           std::fwrite(blk.data(), 4, n * NWP, f) == n * NWP;
-    }
-    ok = ok && host_.write_meta(f);
-    std::vector<u64> mblk;
-    for (u64 b = base_; ok && b < total_; b += kCkptBlock) {
-      const u64 n = std::min<u64>(kCkptBlock, total_ - b);
-      mblk.resize(n);
-      ok = hipMemcpy(mblk.data(), d_meta_ + (b - base_), n * 8, hipMemcpyDeviceToHost) == hipSuccess &&
-           std::fwrite(mblk.data(), 8, n, f) == n;
-    }
-    ok = (std::fclose(f) == 0) && ok;
-    if (!ok || std::rename(tmp.c_str(), path.c_str()) != 0) { err = "writing checkpoint " + path + " failed"; return MC_E_IO; }
-    return 0;
+    h.nwp = NWP; h.total = store_.total(); h.level_begin = level_begin; h.level_count = level_count;
+    ckpt_of_run(r, desc, h);
+    return ckpt::write_file(path, h, desc, r.act_generated, r.act_distinct, r.levels, [&](FILE* f) { return store_.write_body(f); }, err);
   }
   int load_checkpoint(const std::string& path, RunResult& r, u64& level_begin, u64& level_count, std::string& err) {
-    FILE* f = std::fopen(path.c_str(), "rb");
-    if (!f) { err = "cannot read checkpoint " + path; return MC_E_IO; }
-    CkptHead h;
-    const std::string desc = describe_json();
-    std::string fdesc;
-    bool ok = std::fread(&h, sizeof h, 1, f) == 1 && std::memcmp(h.magic, "RAFTMCM1", 8) == 0 && h.nwp == (u64)NWP &&
-              h.n_act == MA_NACT && h.desc_len >= 0 && h.desc_len < (1 << 20) && h.n_levels > 0 && h.n_levels < (1 << 20) &&
-              h.sym_tlc == rt_host_.sym_tlc;
-    if (ok) { fdesc.resize((size_t)h.desc_len); ok = std::fread(&fdesc[0], 1, fdesc.size(), f) == fdesc.size(); }
-    if (!ok || fdesc != desc) { std::fclose(f); err = "checkpoint " + path + " is not a checkpoint of this model"; return MC_E_INVALID; }
-    // completed levels that do not fit the device store stay in host memory (spilled)
-    const u64 lb = h.total > cap_ ? h.level_begin : 0;
-    if (h.level_begin > h.total || h.total - lb > cap_) { std::fclose(f); err = "checkpoint frontier exceeds the state store (raise state_store_bytes)"; return MC_E_OOM; }
-    ok = std::fread(r.act_generated.data(), 8, MA_NACT, f) == (size_t)MA_NACT &&
-         std::fread(r.act_distinct.data(), 8, MA_NACT, f) == (size_t)MA_NACT;
-    r.levels.clear();
-    for (int64_t k = 0; ok && k < h.n_levels; ++k) {
-      LevelStat lv;
-      ok = std::fread(&lv.states, 8, 1, f) == 1 && std::fread(&lv.generated, 8, 1, f) == 1;
-      r.levels.push_back(lv);
-    }
     HIPCHK(hipMemsetAsync(d_ctr_, 0, C_NCTR * 8, stream_));
     HIPCHK(hipStreamSynchronize(stream_));
-    // states: the host part stays on the host and its fingerprints go in through the (idle)
-    // candidate buffer; the device part is read block by block into the store
-    host_.clear();
-    u32* hs = nullptr; u64* hm = nullptr;
-    if (lb) host_.append(lb, &hs, &hm);
-    ok = ok && std::fread(hs, 4, lb * NWP, f) == lb * NWP;
+    ckpt::MembHead h;
+    ckpt::Reader in(path);
+    if (int rc = in.head("RAFTMCM1", NWP, MA_NACT, describe_json(), h, r.act_generated, r.act_distinct, r.levels, err)) return rc;
+    if (h.sym_tlc != rt_host_.sym_tlc) return in.other_model(err);
+    auto reinsert = [&](const u32* states, u64 n) {
+      const dim3 grid((unsigned)((n + BS - 1) / BS));
+      if (rt_dev_.sym_tlc)
+        hipLaunchKernelGGL((memb_reinsert<S, true>), grid, dim3(BS), 0, stream_, states, n, (u64)h.seed, rt_dev_, d_table_, table_mask_, (unsigned long long*)d_ctr_);
+      else
+        hipLaunchKernelGGL((memb_reinsert<S, false>), grid, dim3(BS), 0, stream_, states, n, (u64)h.seed, rt_dev_, d_table_, table_mask_, (unsigned long long*)d_ctr_);
+    };
+    // the host part's fingerprints go in through the (idle) candidate buffer, chunk by chunk
     const u64 stage = std::max<u64>(1, chunk_ * S::NSLOT * 8 / (NWP * 4));
-    for (u64 b = 0; ok && b < lb; b += stage) {
-      const u64 n = std::min<u64>(stage, lb - b);
-      HIPCHK(hipMemcpy(d_cand_, hs + b * NWP, n * NWP * 4, hipMemcpyHostToDevice));
-      if (int rc = launch_reinsert((const u32*)d_cand_, n, h.seed, err)) return rc;
-      HIPCHK(hipStreamSynchronize(stream_));
-    }
-    std::vector<u32> blk;
-    for (u64 b = lb; ok && b < h.total; b += kCkptBlock) {
-      const u64 n = std::min<u64>(kCkptBlock, h.total - b);
-      blk.resize(n * NWP);
-      ok = std::fread(blk.data(), 4, n * NWP, f) == n * NWP;
-      if (ok) HIPCHK(hipMemcpy(d_states_ + (b - lb) * NWP, blk.data(), n * NWP * 4, hipMemcpyHostToDevice));
-    }
-    ok = ok && std::fread(hm, 8, lb, f) == lb;
-    std::vector<u64> mblk;
-    for (u64 b = lb; ok && b < h.total; b += kCkptBlock) {
-      const u64 n = std::min<u64>(kCkptBlock, h.total - b);
-      mblk.resize(n);
-      ok = std::fread(mblk.data(), 8, n, f) == n;
-      if (ok) HIPCHK(hipMemcpy(d_meta_ + (b - lb), mblk.data(), n * 8, hipMemcpyHostToDevice));
-    }
-    std::fclose(f);
-    if (!ok) { host_.clear(); err = "checkpoint " + path + " is truncated"; return MC_E_IO; }
-    if (h.total > lb)
-      if (int rc = launch_reinsert(d_states_, h.total - lb, h.seed, err)) return rc;
-    u64 e = 0;
-    HIPCHK(hipMemcpyAsync(&e, d_ctr_ + C_ERR, 8, hipMemcpyDeviceToHost, stream_));
-    HIPCHK(hipStreamSynchronize(stream_));
-    if (e) { err = "fingerprint table too small for the checkpoint (raise fp_table_bytes)"; return MC_E_OOM; }
-    base_ = lb;
-    r.seed = h.seed; r.generated = h.generated; r.distinct = h.distinct; r.depth = h.depth;
-    r.generated_in_model = h.generated_in_model;
-    total_ = h.total; level_begin = h.level_begin; level_count = h.level_count;
-    return 0;
-  }
-  int launch_reinsert(const u32* states, u64 n, u64 seed, std::string& err) {
-    const dim3 grid((unsigned)((n + BS - 1) / BS));
-    if (rt_dev_.sym_tlc)
-      hipLaunchKernelGGL((memb_reinsert<S, true>), grid, dim3(BS), 0, stream_, states, n, seed, rt_dev_, d_table_, table_mask_, (unsigned long long*)d_ctr_);
-    else
-      hipLaunchKernelGGL((memb_reinsert<S, false>), grid, dim3(BS), 0, stream_, states, n, seed, rt_dev_, d_table_, table_mask_, (unsigned long long*)d_ctr_);
-    HIPCHK(hipGetLastError());
-    return 0;
-  }
-
-  // move the completed levels [base_, level_begin) to host memory and the frontier to the front
-  // of the device store (left shift by d in blocks of <= d slots: each block's target only
-  // overlaps blocks already moved)
-  int spill(u64 level_begin, u64 level_count, std::string& err) {
-    const u64 d = level_begin - base_;
-    u32* hs = nullptr; u64* hm = nullptr;
-    host_.append(d, &hs, &hm);   // a segment of its own: the host part is never reallocated
-    HIPCHK(hipStreamSynchronize(stream_));
-    HIPCHK(hipMemcpy(hs, d_states_, d * NWP * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(hm, d_meta_, d * 8, hipMemcpyDeviceToHost));
-    for (u64 off = 0; off < level_count; off += d) {
-      const u64 n = std::min<u64>(d, level_count - off);
-      HIPCHK(hipMemcpyAsync(d_states_ + off * NWP, d_states_ + (d + off) * NWP, n * NWP * 4, hipMemcpyDeviceToDevice, stream_));
-      HIPCHK(hipMemcpyAsync(d_meta_ + off, d_meta_ + d + off, n * 8, hipMemcpyDeviceToDevice, stream_));
-      HIPCHK(hipStreamSynchronize(stream_));
-    }
-    base_ = level_begin;
+    if (int rc = store_.read_body(in, h.total, h.level_begin, d_cand_, stage, stream_, d_ctr_ + C_ERR, reinsert, err)) return rc;
+    run_of_ckpt(h, r);
+    level_begin = h.level_begin; level_count = h.level_count;
     return 0;
   }
 
   // The first event of the level: reproduce TLC's (the oracle's) stop point, counts and trace.
-  void handle_event(const u64* c, u64 cnt, u64 level_begin, u64 level_count, u64 rank0, int64_t gen_before_chunk,
-                    u64 new_before_chunk, u64 nnew, u32 level, RunResult& r, int pos = -1, u32 pending = 0) {
+  int handle_event(const u64* c, u64 cnt, u64 level_begin, u64 level_count, u64 rank0, int64_t gen_before_chunk,
+                   u64 new_before_chunk, u64 nnew, u32 level, RunResult& r, std::string& err, int pos = -1, u32 pending = 0) {
     // continue mode: pos >= 0 names a violation's invariant by its cfg position; pending != 0 names an
     // erroring invariant among those positions (the plain run: check_invariants' first hit)
     const u64 ev = c[C_EVENT], key = ev >> 2;
@@ -1492,25 +1382,26 @@ class MembGpu : public Backend {
       if (k < key || (k == key && kind >= EV_INV_ERROR)) ++before;
     }
     r.generated += gen;
-    r.distinct = (int64_t)(total_ + new_before_chunk + before);
+    r.distinct = (int64_t)(store_.total() + new_before_chunk + before);
     // TLC's queue at the stop point (oracle/engine.h): the level's parents after this one and the
     // new states found before it
     r.left_on_queue = (int64_t)(level_count - rank - 1 + new_before_chunk + before);
-    W s;
-    read_state(gid, s);
+    u32 w[NWP]; u64 meta = 0;
+    if (!store_.read(gid, w, &meta)) { err = "event state readback failed"; return MC_E_NO_DEVICE; }
+    W s; S::unpack(w, s);
     int k, sub;
     S::inst_of_slot((int)slot, k, sub);
     if (kind == EV_DEADLOCK) {
       r.verdict = MC_VERDICT_DEADLOCK;
-      build_trace(gid, nullptr, s, r);
-      return;
+      build_trace(gid, nullptr, s, r, err);
+      return 0;
     }
     if (kind == EV_NEXT_ERROR) {
       r.verdict = MC_VERDICT_EVAL_ERROR;
       r.error = "TLC evaluation error while computing the successors of state " + std::to_string(gid) +
                 " (SubSeq index out of domain, raft.tla:551/764)";
-      build_trace(gid, nullptr, s, r);
-      return;
+      build_trace(gid, nullptr, s, r, err);
+      return 0;
     }
     W t; u32 e2 = 0;
     const int act = S::apply(s, k, sub, t, e2, rt_host_);
@@ -1529,7 +1420,8 @@ class MembGpu : public Backend {
       r.violated = kMembInvNames[id];
     }
     r.depth = (int64_t)level + 2;   // the successor's depth (oracle: level + 1, Init = 1)
-    build_trace(gid, act >= 0 ? kMembActNames[act] : "?", t, r);
+    build_trace(gid, act >= 0 ? kMembActNames[act] : "?", t, r, err);
+    return 0;
   }
 
   // TLC's per-action (generated, distinct) counters at the stop point: the level's earlier chunks
@@ -1571,20 +1463,8 @@ class MembGpu : public Backend {
   }
 
   int dump_states(const std::string& path, std::string& err) override {
-    if (!d_states_) { err = "mc_dump_states before mc_run"; return MC_E_STATE; }
-    std::vector<u32> h((total_ - base_) * NWP);
-    HIPCHK(hipMemcpy(h.data(), d_states_, h.size() * 4, hipMemcpyDeviceToHost));
-    FILE* f = std::fopen(path.c_str(), "w");
-    if (!f) { err = "cannot write " + path; return MC_E_IO; }
-    for (u64 g = 0; g < total_; ++g) {
-      u32 w[NWP];
-      const u32* src = g < base_ ? host_.state(g) : h.data() + (g - base_) * NWP;
-      for (int q = 0; q < NWP; ++q) w[q] = src[q];
-      W s; S::unpack(w, s);
-      std::fprintf(f, "%s\n", text_.text(s, false).c_str());
-    }
-    std::fclose(f);
-    return 0;
+    if (!store_.states()) { err = "mc_dump_states before mc_run"; return MC_E_STATE; }
+    return rmc::dump_states<NWP>(store_, path, [&](const u32 (&w)[NWP]) { return words_text(w, false); }, err);
   }
 
   // ---- sharded mode: FIFO first-found across ranks.  Per level the driver
@@ -1594,7 +1474,7 @@ class MembGpu : public Backend {
   // all-to-all / store that gives every rank an equal contiguous slice of the next level.
   int shard_open(const RunOpts& o, int rank, int world, std::string& err) override {
     if (world < 1 || world > 8 || rank < 0 || rank >= world) { err = "world must be 1..8"; return MC_E_INVALID; }
-    base_ = 0; host_.clear();   // sharded runs keep every state on the device
+    store_.reset();   // sharded runs keep every state on the device
     for (int q = 0; q < 2; ++q)
       if (((m_.rt.constraints >> kPrefixCon[q]) & 1u) && !have_prefix_[q]) {
         err = std::string(kMembConNames[kPrefixCon[q]]) + " needs its golden history trace (mc_set_history_prefix)";
@@ -1621,7 +1501,7 @@ class MembGpu : public Backend {
       HIPCHK(hipMalloc(&d_lvl_, lvl_cap_ * 16));
       HIPCHK(hipMalloc(&d_sorted_, lvl_cap_ * 8));
       HIPCHK(hipMalloc(&d_newrec_lvl_, lvl_cap_ * 8));
-      HIPCHK(hipMalloc(&d_nsucc_lvl_, cap_ * 2));
+      HIPCHK(hipMalloc(&d_nsucc_lvl_, store_.cap() * 2));
       sort_tmp_bytes_ = 0;
       HIPCHK(rocprim::radix_sort_keys(nullptr, sort_tmp_bytes_, (const u64*)nullptr, (u64*)nullptr, (size_t)lvl_cap_, 0, 48,
                                       stream_));
@@ -1641,7 +1521,7 @@ class MembGpu : public Backend {
     W s0; S::init(s0);
     sres_.generated = 1; sres_.depth = 1;
     sres_.levels.push_back({1, 0, 0.0});
-    s_level_ = 0; s_level_begin_ = 0; s_level_count_ = 0; total_ = 0;
+    s_level_ = 0; s_level_begin_ = 0; s_level_count_ = 0; store_.set_total(0);
     if (!S::in_model(s0, s0, rt_host_)) { sres_.distinct = 0; sres_.depth = 0; s_finished_ = true; finish(sres_, t0_); return 0; }
     const u64 fp0 = S::fingerprint(s0, sres_.seed, rt_host_);
     if (fp_owner(fp0, (u32)world) == (u32)rank) {
@@ -1651,10 +1531,10 @@ class MembGpu : public Backend {
     if (rank == 0) {
       u32 w0[S::NW]; S::pack(s0, w0);
       u32 wp[NWP] = {0}; for (int q = 0; q < S::NW; ++q) wp[q] = w0[q];
-      HIPCHK(hipMemcpy(d_states_, wp, NWP * 4, hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(store_.states(), wp, NWP * 4, hipMemcpyHostToDevice));
       const u64 nometa = ~0ull;
-      HIPCHK(hipMemcpy(d_meta_, &nometa, 8, hipMemcpyHostToDevice));
-      total_ = 1; s_level_count_ = 1;
+      HIPCHK(hipMemcpy(store_.meta(), &nometa, 8, hipMemcpyHostToDevice));
+      store_.set_total(1); s_level_count_ = 1;
     }
     sres_.distinct = 1;
     if (u32 bad = S::check_invariants(s0, rt_host_)) {
@@ -1696,7 +1576,7 @@ class MembGpu : public Backend {
     const u64 cnt = gen_cnt_, nslots = cnt * (u64)S::NSLOT;
     const u32 nblk = (u32)((cnt + BS - 1) / BS);
     MGenArgs g;
-    g.states = d_states_; g.chunk_begin = s_level_begin_ + gen_begin_; g.chunk_count = cnt; g.rank0 = s_B_ + gen_begin_;
+    g.states = store_.states(); g.chunk_begin = s_level_begin_ + gen_begin_; g.chunk_count = cnt; g.rank0 = s_B_ + gen_begin_;
     g.cand = d_cand_; g.cells = d_cells_; g.cells_oom = d_cells_oom_; g.cell_count = d_cell_count_; g.nsucc = d_nsucc_;
     g.seed = sres_.seed; g.rt = rt_dev_; g.inv_oom = sopts_.inv_out_of_model ? 1u : 0u;
     g.deadlock = sopts_.check_deadlock ? 1u : 0u; g.ctr = (unsigned long long*)d_ctr_;
@@ -1751,7 +1631,7 @@ class MembGpu : public Backend {
     if (what == MC_SHARD_STATES) {   // this rank's new states, in key order (one contiguous run)
       if (!nnew_) return 0;
       hipLaunchKernelGGL((memb_pack_states<NWP>), dim3((unsigned)((nnew_ + BS - 1) / BS)), dim3(BS), 0, stream_,
-                         (const u32*)d_states_, (const u64*)d_meta_, total_, nnew_, (u32*)dst);
+                         (const u32*)store_.states(), (const u64*)store_.meta(), store_.total(), nnew_, (u32*)dst);
       HIPCHK(hipGetLastError());
       HIPCHK(hipStreamSynchronize(stream_));
       return 0;
@@ -1804,7 +1684,7 @@ class MembGpu : public Backend {
     n_sorted_ = n; nnew_ = 0;
     if (!n) return 0;
     if (n > lvl_cap_) { sres_err_ |= MERR_STORE; n_sorted_ = 0; return 0; }
-    if (total_ + n > cap_) { sres_err_ |= MERR_STORE; n_sorted_ = 0; return 0; }
+    if (store_.total() + n > store_.cap()) { sres_err_ |= MERR_STORE; n_sorted_ = 0; return 0; }
     size_t tb = sort_tmp_bytes_;
     HIPCHK(hipEventRecord(ev_[5], stream_));
     HIPCHK(rocprim::radix_sort_keys(d_sort_tmp_, tb, (const u64*)acks, d_sorted_, (size_t)n, 0, 48, stream_));
@@ -1812,7 +1692,7 @@ class MembGpu : public Backend {
                        (u64)S::NSLOT, s_B_, s_level_begin_, d_newrec_lvl_);
     HIPCHK(hipGetLastError());
     MMatArgs m;
-    m.states = d_states_; m.meta = d_meta_; m.newrec = d_newrec_lvl_; m.n_new = n; m.dst_base = total_; m.cap = cap_;
+    m.states = store_.states(); m.meta = store_.meta(); m.newrec = d_newrec_lvl_; m.n_new = n; m.dst_base = store_.total(); m.cap = store_.cap();
     m.level_begin = s_level_begin_ - s_B_;   // gid - level_begin = global rank (mod 2^64)
     m.gid_tag = (u64)s_rank_ << 37; m.rt = rt_dev_; m.ctr = (unsigned long long*)d_ctr_;
     if (rt_dev_.sym_tlc) hipLaunchKernelGGL((memb_materialize<S, true>), dim3((unsigned)((n + BS - 1) / BS)), dim3(BS), 0, stream_, m);
@@ -1827,16 +1707,16 @@ class MembGpu : public Backend {
   }
   // the received slice of the next level, appended to the store (replacing the staged new states)
   int shard_store(const void* states, int64_t n, std::string& err) override {
-    if (total_ + (u64)n > cap_) { err = "state store full (raise state_store_bytes)"; return MC_E_OOM; }
+    if (store_.total() + (u64)n > store_.cap()) { err = "state store full (raise state_store_bytes)"; return MC_E_OOM; }
     if (n > 0) {
       hipLaunchKernelGGL((memb_unpack_states<NWP>), dim3((unsigned)((n + BS - 1) / BS)), dim3(BS), 0, stream_, (const u32*)states,
-                         (u64)n, total_, d_states_, d_meta_);
+                         (u64)n, store_.total(), store_.states(), store_.meta());
       HIPCHK(hipGetLastError());
       HIPCHK(hipStreamSynchronize(stream_));
     }
-    s_level_begin_ = total_;
+    s_level_begin_ = store_.total();
     s_level_count_ = (u64)n;
-    total_ += (u64)n;
+    store_.set_total(store_.total() + (u64)n);
     nnew_ = 0;
     return 0;
   }
@@ -1881,15 +1761,15 @@ class MembGpu : public Backend {
     {   // this rank's share of TLC's per-action counters at the stop point ([8, 8+A) generated, [40, 40+A) distinct)
       const u64 npar = R < s_B_ ? 0 : std::min<u64>(s_level_count_, R - s_B_ + 1);
       u64 ag[MA_NACT], ad[MA_NACT];
-      if (int rc = stop_counts_dev(d_states_, s_level_begin_, npar, R - std::min<u64>(R, s_B_), (int)slot, (u32)kind,
-                                   d_meta_ + total_, (u64)before, ag, ad)) { err = "stop-point counters"; return rc; }
+      if (int rc = stop_counts_dev(store_.states(), s_level_begin_, npar, R - std::min<u64>(R, s_B_), (int)slot, (u32)kind,
+                                   store_.meta() + store_.total(), (u64)before, ag, ad)) { err = "stop-point counters"; return rc; }
       for (int k = 0; k < MA_NACT; ++k) { st[8 + k] = (int64_t)ag[k]; st[40 + k] = (int64_t)ad[k]; }
     }
     if (R >= s_B_ && R < s_B_ + s_level_count_) {   // the event's parent is ours: the counterexample head
       const u64 gid = s_level_begin_ + (R - s_B_);
-      W s; read_state(gid, s);
-      u64 meta = 0;
-      HIPCHK(hipMemcpy(&meta, d_meta_ + gid, 8, hipMemcpyDeviceToHost));
+      u32 w[NWP]; u64 meta = 0;
+      if (!store_.read(gid, w, &meta)) { err = "event state readback failed"; return MC_E_NO_DEVICE; }
+      W s; S::unpack(w, s);
       have_viol_ = true;
       if (kind == EV_DEADLOCK || kind == EV_NEXT_ERROR) {   // the trace ends at the parent itself
         viol_parent_ = meta == ~0ull ? ~0ull : (meta >> 20);
@@ -1956,17 +1836,17 @@ class MembGpu : public Backend {
     if (g[0] == 0) *done = 1;
     else if (sopts_.max_depth && sres_.depth >= sopts_.max_depth) { sres_.verdict = MC_VERDICT_DEPTH_LIMIT; sres_.left_on_queue = g[0]; *done = 1; }
     if (*done) {   // the last level stays where it was generated (no rebalance follows)
-      total_ += nnew_; nnew_ = 0;
+      store_.set_total(store_.total() + nnew_); nnew_ = 0;
       s_finished_ = true; finish(sres_, t0_);
     }
     return 0;
   }
   int shard_read_state(uint64_t gid, std::string& text, uint64_t* meta, std::string& err) const override {
     const u64 local = gid & ((1ull << 37) - 1);
-    if (local >= total_) { err = "state id out of range"; return MC_E_INVALID; }
-    W s; read_state(local, s);
-    u64 m = 0;
-    if (hipMemcpy(&m, d_meta_ + local, 8, hipMemcpyDeviceToHost) != hipSuccess) { err = "hipMemcpy failed"; return MC_E_NO_DEVICE; }
+    if (local >= store_.total()) { err = "state id out of range"; return MC_E_INVALID; }
+    u32 w[NWP]; u64 m = 0;
+    if (!store_.read(local, w, &m)) { err = "hipMemcpy failed"; return MC_E_NO_DEVICE; }
+    W s; S::unpack(w, s);
     text = text_.text(s, true);
     // normalised as the raft_original records: parent gid << 24 | action << 16
     if (meta) *meta = m == ~0ull ? ~0ull : ((m >> 20) << 24) | (((m >> 10) & 1023) << 16);
@@ -1989,7 +1869,7 @@ class MembGpu : public Backend {
  private:
   MembModel m_;
   MembText<S> text_;
-  u64* d_table_ = nullptr; u32* d_states_ = nullptr; u64* d_meta_ = nullptr; u64* d_ctr_ = nullptr;
+  u64* d_table_ = nullptr; u64* d_ctr_ = nullptr;
   u64* d_cand_ = nullptr; u64* d_newrec_ = nullptr; unsigned short* d_nsucc_ = nullptr; unsigned int* d_woff_ = nullptr;
   u32* d_cells_ = nullptr; u32* d_cells_oom_ = nullptr; u32* d_cell_count_ = nullptr; u32* d_big_ = nullptr;
   u64* d_smask_ = nullptr;   // [SMW][chunk] in-model slot masks (single-GPU loop)
@@ -2001,11 +1881,9 @@ class MembGpu : public Backend {
   u64* d_bsum_ = nullptr;
   hipStream_t stream_ = nullptr;
   hipEvent_t ev_[9] = {};
-  u64 table_mask_ = 0, cap_ = 0, total_ = 0, chunk_ = 0;
+  u64 table_mask_ = 0, chunk_ = 0;
   int dev_ = -1; uint64_t req_table_ = 0, req_store_ = 0;
-  // completed levels moved to host memory: global ids [0, base_) live in host_ (segments)
-  u64 base_ = 0;
-  HostStore host_{NWP};
+  StateStore store_;   // the stored states and parent pointers: device part + host spill
 
   // sharded mode
   RunOpts sopts_;
@@ -2073,48 +1951,23 @@ class MembGpu : public Backend {
     for (auto& p : d_ptab_) { if (p) (void)hipFree(p); p = nullptr; }
     for (void* q : {(void*)d_lvl_, (void*)d_sorted_, (void*)d_newrec_lvl_, (void*)d_sort_tmp_, (void*)d_nsucc_lvl_}) if (q) (void)hipFree(q);
     d_lvl_ = nullptr; d_sorted_ = nullptr; d_newrec_lvl_ = nullptr; d_sort_tmp_ = nullptr; d_nsucc_lvl_ = nullptr; lvl_cap_ = 0;
-    for (void* p : {(void*)d_table_, (void*)d_states_, (void*)d_meta_, (void*)d_ctr_, (void*)d_cand_, (void*)d_newrec_,
+    for (void* p : {(void*)d_table_, (void*)d_ctr_, (void*)d_cand_, (void*)d_newrec_,
                     (void*)d_nsucc_, (void*)d_woff_, (void*)d_bsum_, (void*)d_cells_, (void*)d_cells_oom_, (void*)d_cell_count_, (void*)d_big_, (void*)d_smask_})
       if (p) (void)hipFree(p);
     for (auto& e : ev_) { if (e) (void)hipEventDestroy(e); e = nullptr; }
     for (auto& e : ev_w_) { if (e) (void)hipEventDestroy(e); e = nullptr; }
     if (d_wit_) { (void)hipFree(d_wit_); d_wit_ = nullptr; }
     if (stream_) (void)hipStreamDestroy(stream_);
-    d_table_ = nullptr; d_states_ = nullptr; d_meta_ = nullptr; d_ctr_ = nullptr; d_cand_ = nullptr; d_newrec_ = nullptr;
+    store_.release();
+    d_table_ = nullptr; d_ctr_ = nullptr; d_cand_ = nullptr; d_newrec_ = nullptr;
     d_nsucc_ = nullptr; d_woff_ = nullptr; d_bsum_ = nullptr; d_cells_ = nullptr; d_cells_oom_ = nullptr; d_cell_count_ = nullptr; d_big_ = nullptr; d_smask_ = nullptr; stream_ = nullptr;
   }
-  // stored state `gid` (global id) and its parent pointer, from the host part or the device
-  void read_state(u64 gid, W& s, u64* meta = nullptr) const {
-    u32 w[NWP];
-    if (gid < base_) {
-      std::memcpy(w, host_.state(gid), NWP * 4);
-      if (meta) *meta = host_.meta(gid);
-    } else {
-      (void)hipMemcpy(w, d_states_ + (gid - base_) * NWP, NWP * 4, hipMemcpyDeviceToHost);
-      if (meta) (void)hipMemcpy(meta, d_meta_ + (gid - base_), 8, hipMemcpyDeviceToHost);
-    }
-    S::unpack(w, s);
+  // a parent pointer: the action in bits 10..19, the parent's global id from bit 20 up
+  void build_trace(u64 parent, const char* last_act, const W& last, RunResult& r, std::string& err) {
+    rmc::build_trace<NWP>(store_, parent, last_act, last_act ? text_.text(last, true) : std::string(),
+                          [&](const u32 (&w)[NWP]) { return words_text(w, true); }, kMembActNames, 10, 1023, 20, r.trace, err);
   }
-  void finish(RunResult& r, std::chrono::steady_clock::time_point t0) {
-    const double M = (double)r.distinct, Ng = (double)r.generated;
-    r.collision_optimistic = M * (Ng - M) / 18446744073709551616.0;
-    r.seconds_total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  }
-  // parent-pointer chase on the host (<= depth device reads)
-  void build_trace(u64 parent, const char* last_act, const W& last, RunResult& r) {
-    std::vector<std::pair<std::string, std::string>> tr;
-    if (last_act) tr.push_back({last_act, text_.text(last, true)});
-    u64 g = parent;
-    while (true) {
-      W s; u64 meta = 0;
-      read_state(g, s, &meta);
-      if (meta == ~0ull) { tr.push_back({"<Initial predicate>", text_.text(s, true)}); break; }
-      tr.push_back({kMembActNames[(meta >> 10) & 1023], text_.text(s, true)});
-      g = meta >> 20;
-    }
-    std::reverse(tr.begin(), tr.end());
-    r.trace = tr;
-  }
+  std::string words_text(const u32 (&w)[NWP], bool multiline) const { W s; S::unpack(w, s); return text_.text(s, multiline); }
 };
 
 // ------------------------------------------------------------------ shapes compiled into this build: (N, NV)

@@ -52,12 +52,12 @@
 #include "../../include/raftmc.h"
 #include "backend.h"
 #include "fp_gap.h"
-#include "host_store.h"
 #include "orig_spec.h"
 #include "orig_text.h"
 #include "rccl_api.h"
 #include "shard_transport.h"
 #include "sim_rng.h"
+#include "state_store.h"
 
 namespace rmc {
 
@@ -123,7 +123,7 @@ struct GenArgs {
 //  * DuplicateMessage / DropMessage unrolled per bag slot, without apply or pack.
 // In-model successors leave as compacted records: per instance a wave ballot and consecutive stores
 // into the wave's own region (only ~21% of C2's instance slots carry an in-model successor).
-// Rejected designs (measured on MI355X; scripts/variants/orig_backend_experiments.hip builds them):
+// Rejected designs (measured on MI355X: DESIGN.md §4; their code is in the repository's history):
 // instances binned by family for every family (19.5 vs 14.5 ms, round 4: a per-lane instance turns
 // apply's whole dispatch into vector work), patch packing from the parent's words (14.45 vs 13.37 ms,
 // round 5), per-wave aggregated action counts (+1.3 ms, round 2), DuplicateMessage / DropMessage
@@ -487,7 +487,7 @@ struct WaveRegions {
 // Workgroup-local first-come fingerprint filter: answers only "certainly produced here before"
 // (a full probe window lets the record through: the seen-set decides).  An empty slot is claimed
 // by LDS CAS, so the set is exact up to the window: with plain stores (the round-4
-// form, scripts/variants/orig_backend_experiments.hip RMC_LDS_PLAIN) two lanes inserting different fingerprints into one slot at once left one of them out of
+// form) two lanes inserting different fingerprints into one slot at once left one of them out of
 // the set, and two lanes with the same fingerprint both passed.  Measured on C2 (round 5,
 // profiles/r05_dedup_ab.txt): 339.5M seen-set probes per run instead of 367.0M, orig_dedup_plain
 // 11.30 vs 11.51 ms; a 16-slot window changed nothing (366.5M: overflow is not the leak) and an
@@ -1432,19 +1432,17 @@ class OrigGpu : public Backend {
     uint64_t slots = 1; while (slots * 2 * 16 <= tb) slots *= 2;   // 16-B entries {fp, ~key}
     if (slots < 1024) slots = 1024;
     uint64_t sb = o.state_store_bytes ? o.state_store_bytes : std::min<uint64_t>(32ull << 30, freeb / 3);
-    cap_ = sb / (NWP * 4 + 8);
-    if (cap_ < 16) cap_ = 16;
+    const u64 cap = std::max<u64>(16, sb / (NWP * 4 + 8));
     // frontier chunk: the record regions hold chunk_states * NI records (10 B each), their
     // distinct pairs (16 B) and the inserted-position list as many 8-B entries (worst case: every
     // record new), sharded mode also world route regions of 16-B records: ~1/4 of the store
-    chunk_states_ = std::max<u64>(4096, std::min<u64>(cap_, (sb / 4) / ((34 + 16 * (u64)world) * (u64)S::NI)));
+    chunk_states_ = std::max<u64>(4096, std::min<u64>(cap, (sb / 4) / ((34 + 16 * (u64)world) * (u64)S::NI)));
     chunk_states_ = std::min<u64>(chunk_states_, (u64)SCAN_BS * 64 * BS);   // orig_scan: <= 64 blocks per lane
     chunk_states_ = (chunk_states_ / BS) * BS;   // whole workgroups: records are grouped per generate workgroup
     const u64 nblk = chunk_states_ / BS, nrec = chunk_states_ * (u64)S::NI;
     table_mask_ = slots - 1;
     HIPCHK(hipMalloc(&d_table_, slots * 16));
-    HIPCHK(hipMalloc(&d_states_, cap_ * NWP * 4));
-    HIPCHK(hipMalloc(&d_meta_, cap_ * 8));
+    HIPCHK(store_.alloc(cap, NWP));
     HIPCHK(hipMalloc(&d_rfp_, nrec * 8));
     HIPCHK(hipMalloc(&d_rkey_, nrec * 2));
     HIPCHK(hipMalloc(&d_rcnt_blk_, nblk * 16));
@@ -1510,7 +1508,7 @@ class OrigGpu : public Backend {
 
   GenArgs gen_args(u64 dev_begin, u64 count, u64 gid0, u64 seed, const RunOpts& o) const {
     GenArgs g;
-    g.states = d_states_; g.chunk_begin = dev_begin; g.chunk_count = count; g.gid0 = gid0;
+    g.states = store_.states(); g.chunk_begin = dev_begin; g.chunk_count = count; g.gid0 = gid0;
     g.rfp = d_rfp_; g.rkey = d_rkey_; g.rcnt = d_rcnt_blk_; g.seed = seed; g.rt = m_.rt;
     g.inv_oom = o.inv_out_of_model ? 1u : 0u; g.deadlock = o.check_deadlock ? 1u : 0u;
     g.ctr = (unsigned long long*)d_ctr_;
@@ -1706,7 +1704,7 @@ class OrigGpu : public Backend {
     for (int k = 0; k < OA_NACT; ++k) r.action_names.push_back(kOrigActNames[k]);
     r.act_generated.assign(OA_NACT, 0); r.act_distinct.assign(OA_NACT, 0);
     r.kernels = {{"orig_generate", 0, 0, 0}, {"orig_merge_probe", 0, 0, 0}, {"orig_mark_scan", 0, 0, 0}, {"orig_materialize", 0, 0, 0}};
-    base_ = 0; host_.clear();
+    store_.reset();
 
     W s0; S::init(s0);
     const u64 S_B = NWP * 4;
@@ -1719,10 +1717,10 @@ class OrigGpu : public Backend {
     InitWords<NWP> wp = {}; for (int q = 0; q < S::NW; ++q) wp.w[q] = w0[q];
     const u64 fp0 = fp64(w0, r.seed);
     static_assert(NWP <= 64, "orig_init_state: one lane per state word");
-    if (fifo) hipLaunchKernelGGL((orig_init_state<NWP, 2>), dim3(1), dim3(64), 0, stream_, wp, d_states_, d_meta_, tbl, tmask, fp0);
-    else hipLaunchKernelGGL((orig_init_state<NWP, 1>), dim3(1), dim3(64), 0, stream_, wp, d_states_, d_meta_, tbl, tmask, fp0);
+    if (fifo) hipLaunchKernelGGL((orig_init_state<NWP, 2>), dim3(1), dim3(64), 0, stream_, wp, store_.states(), store_.meta(), tbl, tmask, fp0);
+    else hipLaunchKernelGGL((orig_init_state<NWP, 1>), dim3(1), dim3(64), 0, stream_, wp, store_.states(), store_.meta(), tbl, tmask, fp0);
     HIPCHK(hipGetLastError());
-    r.generated = 1; r.distinct = 1; total_ = 1;
+    r.generated = 1; r.distinct = 1; store_.set_total(1);
     r.levels.push_back({1, 1, 0.0});
     r.depth = 1;
     if (!S::in_model(s0, m_.rt) || S::violated(s0, m_.rt.invariants)) HIPCHK(hipStreamSynchronize(stream_));   // the run ends here
@@ -1744,12 +1742,12 @@ class OrigGpu : public Backend {
       // the device keeps what the search still reads (the frontier) and writes (the next
       // level); when the next level, predicted from the last growth ratio with a 1.5x margin,
       // might not fit behind what is stored, the completed levels move to host memory
-      if (level_begin > base_ && !last) {
+      if (level_begin > store_.base() && !last) {
         const double prev = r.levels.size() >= 2 ? (double)r.levels[r.levels.size() - 2].states : 1.0;
         const double pred = (double)level_count * std::max(1.0, (double)level_count / std::max(prev, 1.0)) * 1.5;
-        if ((double)(total_ - base_) + pred > (double)cap_) {
-          if (progress_) std::fprintf(stderr, "spilling %llu completed states to host memory\n", (unsigned long long)(level_begin - base_));
-          if (int rc = spill(level_begin, level_count, err)) return rc;
+        if ((double)(store_.total() - store_.base()) + pred > (double)store_.cap()) {
+          if (progress_) std::fprintf(stderr, "spilling %llu completed states to host memory\n", (unsigned long long)(level_begin - store_.base()));
+          if (int rc = store_.spill(level_begin, level_count, stream_, progress_, err)) return rc;
         }
       }
       if (!ctr_clean_) {
@@ -1789,8 +1787,8 @@ class OrigGpu : public Backend {
         const unsigned nblk = (unsigned)((cnt + BS - 1) / BS);
         if (int rc = lvl_events(nch)) { err = "hipEventCreate failed"; return rc; }
         hipEvent_t* e = &lvl_ev_[8 * nch];
-        // kernels index the device store (global id - base_); keys and parent pointers are global
-        const GenArgs g = gen_args(cb - base_, cnt, cb, r.seed, o);
+        // kernels index the device store (global id - store_.base()); keys and parent pointers are global
+        const GenArgs g = gen_args(cb - store_.base(), cnt, cb, r.seed, o);
         HIPCHK(hipEventRecord(e[0], stream_));
         launch_generate(g, nblk);
         HIPCHK(hipGetLastError());
@@ -1829,14 +1827,14 @@ class OrigGpu : public Backend {
         if (fifo) HIPCHK(hipEventRecord(e[5], stream_));
         if (fifo) {
           MatArgs m;
-          m.states = d_states_; m.meta = d_meta_; m.chunk_begin = cb - base_; m.chunk_count = cnt; m.gid0 = cb;
-          m.winmask = d_winmask_; m.woff = d_woff_; m.ww = WW; m.dst_base = level_end - base_; m.cap = cap_;
+          m.states = store_.states(); m.meta = store_.meta(); m.chunk_begin = cb - store_.base(); m.chunk_count = cnt; m.gid0 = cb;
+          m.winmask = d_winmask_; m.woff = d_woff_; m.ww = WW; m.dst_base = level_end - store_.base(); m.cap = store_.cap();
           m.rt = m_.rt; m.ctr = (unsigned long long*)d_ctr_;
           hipLaunchKernelGGL((orig_materialize<S>), dim3(nblk), dim3(BS), 0, stream_, m);
         } else {
           MatPlainArgs m;
-          m.states = d_states_; m.meta = d_meta_; m.newrec = d_newrec_; m.base = base_; m.dst_base = level_end - base_;
-          m.cap = cap_; m.rt = m_.rt; m.ctr = (unsigned long long*)d_ctr_; m.store = last ? 0u : 1u;
+          m.states = store_.states(); m.meta = store_.meta(); m.newrec = d_newrec_; m.base = store_.base(); m.dst_base = level_end - store_.base();
+          m.cap = store_.cap(); m.rt = m_.rt; m.ctr = (unsigned long long*)d_ctr_; m.store = last ? 0u : 1u;
           hipLaunchKernelGGL((orig_materialize_plain<S>), dim3((unsigned)std::min<u64>(4096, (cnt * 2 + BS - 1) / BS)), dim3(BS), 0, stream_, m);
         }
         HIPCHK(hipGetLastError());
@@ -1880,7 +1878,7 @@ class OrigGpu : public Backend {
                      std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(),
                      (long long)(r.generated + (int64_t)[&] { u64 g = 0; for (int k = 0; k < OA_NACT; ++k) g += c[K_ACT + k]; return g; }()),
                      (unsigned long long)(level_end + nnew), (unsigned long long)nnew, level_ms, nch,
-                     (unsigned long long)((last ? level_end : next_write) - base_), (unsigned long long)cap_, (unsigned long long)base_,
+                     (unsigned long long)((last ? level_end : next_write) - store_.base()), (unsigned long long)store_.cap(), (unsigned long long)store_.base(),
                      last ? "; the last level counted, not stored" : "");
       if (progress_ && (c[K_EVENT] != ~0ull || c[K_ERR]))
         std::fprintf(stderr, "level %lld: event word 0x%llx, error flags 0x%llx\n", (long long)r.depth + 1,
@@ -1900,7 +1898,7 @@ class OrigGpu : public Backend {
       r.kernels[3].algo_bytes += (double)level_count * WW * 8 + (double)nnew * (S_B + S_B + 8);
       r.seconds_kernels += level_ms / 1000.0;
       r.n_launches += 1;
-      if (!last && next_write - base_ > cap_) c[K_ERR] |= OE_CAP_STORE;
+      if (!last && next_write - store_.base() > store_.cap()) c[K_ERR] |= OE_CAP_STORE;
       if (c[K_EVENT] != ~0ull && !fifo && (c[K_ERR] & ~(u64)OE_CAP_STORE) == 0) {
         // TLC -workers N found an event: TLC's counterexample and stop point are the single-worker
         // search's, so the model is searched again in FIFO order (it stops at this level)
@@ -1923,10 +1921,10 @@ class OrigGpu : public Backend {
       if (c[K_EVENT] != ~0ull && (c[K_ERR] & ~(u64)OE_CAP_STORE) == 0) {
         // the level's first event in TLC's order stops the search; a full state store only
         // matters when it cut off states that come before the event in key order
-        const u64 stored = std::min<u64>(nnew, cap_ - std::min<u64>(cap_, level_end - base_));
+        const u64 stored = std::min<u64>(nnew, store_.cap() - std::min<u64>(store_.cap(), level_end - store_.base()));
         bool decided = false;
         if (int rc = handle_event(c[K_EVENT], level_begin, level_count, nnew, stored, r, decided, err)) return rc;
-        if (decided) { total_ = level_end + stored; break; }
+        if (decided) { store_.set_total(level_end + stored); break; }
       }
       if (c[K_ERR]) {
         const u64 e = c[K_ERR];
@@ -1936,15 +1934,15 @@ class OrigGpu : public Backend {
         if (e & OE_CAP_ELECTIONS) os << " elections set exceeds the compiled capacity;";
         if (e & OE_CAP_COUNT) os << " message count / bag capacity exceeded;";
         if (e & OE_CAP_STORE)
-          os << " state store full (raise state_store_bytes): " << cap_ << " state slots, " << base_
+          os << " state store full (raise state_store_bytes): " << store_.cap() << " state slots, " << store_.base()
              << " states on the host, level ends at " << level_end << ", " << nnew << " new;";
         if (e & OE_TABLE_FULL) os << " fingerprint table full (raise fp_table_bytes);";
         // the summary counts the completed levels (their sizes sum to it, and the depth is theirs);
         // whatever part of the interrupted level reached the store is not a level of the search
         os << " the summary counts the " << level_end << " states of the " << r.depth << " completed levels;";
         r.error = os.str();
-        total_ = level_end;
-        r.distinct = (int64_t)total_;
+        store_.set_total(level_end);
+        r.distinct = (int64_t)level_end;
         break;
       }
       int64_t gen = 0;
@@ -1953,9 +1951,9 @@ class OrigGpu : public Backend {
       r.generated_in_model += (int64_t)G_in;
       r.seen_set_probes += (int64_t)c[K_PROBES];
       r.algo_bytes += (double)level_count * S_B + (double)G_in * 8 + (double)nnew * (16 + S_B);
-      if (last) unstored_ = nnew;   // counted, not in the store (total_ counts stored states)
-      else total_ += nnew;
-      r.distinct = (int64_t)(total_ + unstored_);
+      if (last) unstored_ = nnew;   // counted, not in the store (the store's total counts stored states)
+      else store_.set_total(store_.total() + nnew);
+      r.distinct = (int64_t)(store_.total() + unstored_);
       r.levels.back().generated = gen;
       r.levels.back().kernel_ms = level_ms;
       if (nnew > 0) { r.levels.push_back({(int64_t)nnew, 0, 0.0}); r.depth += 1; }
@@ -1991,7 +1989,7 @@ class OrigGpu : public Backend {
     // state itself is new when it is in the model)
     auto key_at = [&](u64 i, u64& kk) -> int {
       u64 mt = 0;
-      HIPCHK(hipMemcpy(&mt, d_meta_ + (level_end - base_) + i, 8, hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(&mt, store_.meta() + (level_end - store_.base()) + i, 8, hipMemcpyDeviceToHost));
       kk = ((mt >> 24) << 8) | (mt & 0xff);
       return 0;
     };
@@ -2016,7 +2014,7 @@ class OrigGpu : public Backend {
     HIPCHK(hipMemsetAsync(d_stop_, 0, (1 + OA_NACT) * 8, stream_));
     const u64 npar = pg - level_begin + 1;
     hipLaunchKernelGGL((orig_stop_generated<S>), dim3((unsigned)((npar + BS - 1) / BS)), dim3(BS), 0, stream_,
-                       (const u32*)d_states_, level_begin - base_, npar, level_begin, pg, k, (u32)kind, (unsigned long long*)d_stop_);
+                       (const u32*)store_.states(), level_begin - store_.base(), npar, level_begin, pg, k, (u32)kind, (unsigned long long*)d_stop_);
     HIPCHK(hipGetLastError());
     u64 gs[1 + OA_NACT];
     HIPCHK(hipMemcpyAsync(gs, d_stop_, sizeof gs, hipMemcpyDeviceToHost, stream_));
@@ -2024,7 +2022,7 @@ class OrigGpu : public Backend {
     HIPCHK(hipMemsetAsync(d_stop_, 0, (1 + OA_NACT) * 8, stream_));
     if (before)
       hipLaunchKernelGGL(orig_stop_distinct, dim3((unsigned)((before + BS - 1) / BS)), dim3(BS), 0, stream_,
-                         (const u64*)(d_meta_ + (level_end - base_)), before, (unsigned long long*)d_stop_);
+                         (const u64*)(store_.meta() + (level_end - store_.base())), before, (unsigned long long*)d_stop_);
     HIPCHK(hipGetLastError());
     u64 ds[1 + OA_NACT];
     HIPCHK(hipMemcpyAsync(ds, d_stop_, sizeof ds, hipMemcpyDeviceToHost, stream_));
@@ -2036,7 +2034,7 @@ class OrigGpu : public Backend {
     r.left_on_queue = (int64_t)(level_end - pg - 1 + before);
     // the event's parent and (for a violation) successor, re-derived on the host
     u32 w[NWP]; u64 meta = 0;
-    if (!stored_state(pg, w, meta)) { err = "event state readback failed"; return MC_E_NO_DEVICE; }
+    if (!store_.read(pg, w, &meta)) { err = "event state readback failed"; return MC_E_NO_DEVICE; }
     W s; S::unpack(w, s);
     if (kind == EV_NEXT_ERROR) {
       r.verdict = MC_VERDICT_EVAL_ERROR;
@@ -2063,158 +2061,45 @@ class OrigGpu : public Backend {
   }
 
   // ---------------------------------------------------------------- checkpoint / recover
-  // File: magic, the model's describe_json (a checkpoint only resumes the same model), the BFS
-  // position (level_begin/count, stored states) and TLC's counters, then the stored states and
-  // parent pointers [0, total).  The seen-set is rebuilt from the states on recovery.
-  // fifo: the search order the stored levels are in — 1 = TLC's single-worker FIFO order (-workers 1:
-  // kept parents, per-action distinct counts and counterexamples are TLC's), 0 = the -workers N
-  // pipeline (first-come dedup).  A -workers N checkpoint cannot resume a -workers 1 search (its
-  // kept parents are not TLC's); the reverse is safe.
-  struct CkptHead {
-    char magic[8];
-    u64 nwp, total, level_begin, level_count, seed;
-    int64_t generated, distinct, depth, generated_in_model, n_act, n_levels, desc_len, fifo;
-  };
+  // ckpt::OrigHead around the shared framing (ckpt_file.h) and store body (state_store.h)
   int save_checkpoint(const std::string& path, const RunResult& r, u64 level_begin, u64 level_count, std::string& err) {
     const std::string desc = describe_json();
-    CkptHead h;
+    ckpt::OrigHead h;
     std::memcpy(h.magic, "RAFTMCK2", 8);
     h.fifo = last_fifo_ ? 1 : 0;
-    h.nwp = NWP; h.total = total_; h.level_begin = level_begin; h.level_count = level_count; h.seed = r.seed;
-    h.generated = r.generated; h.distinct = r.distinct; h.depth = r.depth; h.generated_in_model = r.generated_in_model;
-    h.n_act = OA_NACT; h.n_levels = (int64_t)r.levels.size(); h.desc_len = (int64_t)desc.size();
-    const std::string tmp = path + ".tmp";
-    FILE* f = std::fopen(tmp.c_str(), "wb");
-    if (!f) { err = "cannot write checkpoint " + tmp; return MC_E_IO; }
-    bool ok = std::fwrite(&h, sizeof h, 1, f) == 1 && std::fwrite(desc.data(), 1, desc.size(), f) == desc.size() &&
-              std::fwrite(r.act_generated.data(), 8, OA_NACT, f) == (size_t)OA_NACT &&
-              std::fwrite(r.act_distinct.data(), 8, OA_NACT, f) == (size_t)OA_NACT;
-    for (const auto& lv : r.levels) ok = ok && std::fwrite(&lv.states, 8, 1, f) == 1 && std::fwrite(&lv.generated, 8, 1, f) == 1;
-    // the host part straight from host memory, the device part in bounded blocks (no second copy
-    // of the store in host memory)
-    constexpr u64 BLK = 1u << 20;
-    ok = ok && host_.write_states(f);
-    std::vector<u32> blk;
-    for (u64 b = base_; ok && b < total_; b += BLK) {
-      const u64 n = std::min<u64>(BLK, total_ - b);
-      blk.resize(n * NWP);
-      ok = hipMemcpy(blk.data(), d_states_ + (b - base_) * NWP, n * NWP * 4, hipMemcpyDeviceToHost) == hipSuccess &&
-           std::fwrite(blk.data(), 4, n * NWP, f) == n * NWP;
-    }
-    ok = ok && host_.write_meta(f);
-    std::vector<u64> mblk;
-    for (u64 b = base_; ok && b < total_; b += BLK) {
-      const u64 n = std::min<u64>(BLK, total_ - b);
-      mblk.resize(n);
-      ok = hipMemcpy(mblk.data(), d_meta_ + (b - base_), n * 8, hipMemcpyDeviceToHost) == hipSuccess &&
-           std::fwrite(mblk.data(), 8, n, f) == n;
-    }
-    ok = (std::fclose(f) == 0) && ok;
-    if (!ok || std::rename(tmp.c_str(), path.c_str()) != 0) { err = "writing checkpoint " + path + " failed"; return MC_E_IO; }
-    return 0;
+    h.nwp = NWP; h.total = store_.total(); h.level_begin = level_begin; h.level_count = level_count;
+    ckpt_of_run(r, desc, h);
+    return ckpt::write_file(path, h, desc, r.act_generated, r.act_distinct, r.levels, [&](FILE* f) { return store_.write_body(f); }, err);
   }
   int load_checkpoint(const std::string& path, bool fifo, RunResult& r, u64& level_begin, u64& level_count, std::string& err) {
-    FILE* f = std::fopen(path.c_str(), "rb");
-    if (!f) { err = "cannot read checkpoint " + path; return MC_E_IO; }
-    CkptHead h;
-    const std::string desc = describe_json();
-    std::string fdesc;
-    bool ok = std::fread(&h, sizeof h, 1, f) == 1 && std::memcmp(h.magic, "RAFTMCK2", 8) == 0 && h.nwp == (u64)NWP &&
-              h.n_act == OA_NACT && h.desc_len >= 0 && h.desc_len < (1 << 20) && h.n_levels > 0 && h.n_levels < (1 << 20);
-    if (ok) { fdesc.resize((size_t)h.desc_len); ok = std::fread(&fdesc[0], 1, fdesc.size(), f) == fdesc.size(); }
-    if (!ok || fdesc != desc) { std::fclose(f); err = "checkpoint " + path + " is not a checkpoint of this model"; return MC_E_INVALID; }
+    HIPCHK(hipMemsetAsync(d_ctr_, 0, K_NCTR * 8, stream_));
+    ckpt::OrigHead h;
+    ckpt::Reader in(path);
+    if (int rc = in.head("RAFTMCK2", NWP, OA_NACT, describe_json(), h, r.act_generated, r.act_distinct, r.levels, err)) return rc;
     if (fifo && !h.fifo) {
-      std::fclose(f);
       err = "checkpoint " + path + " was written by a -workers N search: its kept parents are not TLC's single-worker "
             "FIFO ones, so it cannot resume a -workers 1 search";
       return MC_E_INVALID;
     }
-    // completed levels that do not fit the device store stay in host memory (spilled)
-    const u64 lb = h.total > cap_ ? h.level_begin : 0;
-    if (h.total - lb > cap_ || h.level_begin > h.total) { std::fclose(f); err = "checkpoint frontier exceeds the state store (raise state_store_bytes)"; return MC_E_OOM; }
-    ok = std::fread(r.act_generated.data(), 8, OA_NACT, f) == (size_t)OA_NACT &&
-         std::fread(r.act_distinct.data(), 8, OA_NACT, f) == (size_t)OA_NACT;
-    r.levels.clear();
-    for (int64_t k = 0; ok && k < h.n_levels; ++k) {
-      LevelStat lv;
-      ok = std::fread(&lv.states, 8, 1, f) == 1 && std::fread(&lv.generated, 8, 1, f) == 1;
-      r.levels.push_back(lv);
-    }
-    // streamed: the host part into one host segment, the device part block by block into the
-    // store (no second copy of the checkpoint in host memory)
-    host_.clear();
-    u32* hs = nullptr; u64* hm = nullptr;
-    if (lb) host_.append(lb, &hs, &hm);
-    ok = ok && std::fread(hs, 4, lb * NWP, f) == lb * NWP;
-    constexpr u64 BLK = 1u << 20;
-    std::vector<u32> blk;
-    for (u64 b = lb; ok && b < h.total; b += BLK) {
-      const u64 n = std::min<u64>(BLK, h.total - b);
-      blk.resize(n * NWP);
-      ok = std::fread(blk.data(), 4, n * NWP, f) == n * NWP &&
-           hipMemcpy(d_states_ + (b - lb) * NWP, blk.data(), n * NWP * 4, hipMemcpyHostToDevice) == hipSuccess;
-    }
-    ok = ok && std::fread(hm, 8, lb, f) == lb;
-    std::vector<u64> mblk;
-    for (u64 b = lb; ok && b < h.total; b += BLK) {
-      const u64 n = std::min<u64>(BLK, h.total - b);
-      mblk.resize(n);
-      ok = std::fread(mblk.data(), 8, n, f) == n &&
-           hipMemcpy(d_meta_ + (b - lb), mblk.data(), n * 8, hipMemcpyHostToDevice) == hipSuccess;
-    }
-    std::fclose(f);
-    if (!ok) { host_.clear(); err = "checkpoint " + path + " is truncated"; return MC_E_IO; }
-    HIPCHK(hipMemsetAsync(d_ctr_, 0, K_NCTR * 8, stream_));
+    auto reinsert = [&](const u32* states, u64 n) {
+      const dim3 grid((unsigned)((n + BS - 1) / BS));
+      if (last_fifo_)
+        hipLaunchKernelGGL((orig_reinsert<S, 2>), grid, dim3(BS), 0, stream_, states, n, d_table_, table_mask_, (u64)h.seed, (unsigned long long*)d_ctr_);
+      else
+        hipLaunchKernelGGL((orig_reinsert<S, 1>), grid, dim3(BS), 0, stream_, states, n, d_table_, 2 * table_mask_ + 1, (u64)h.seed, (unsigned long long*)d_ctr_);
+    };
     // the host part's fingerprints go in through the (idle) candidate buffer, chunk by chunk
     const u64 stage = std::max<u64>(1, chunk_states_ * S::NI * 8 / (NWP * 4));
-    for (u64 b = 0; b < lb; b += stage) {
-      const u64 n = std::min<u64>(stage, lb - b);
-      HIPCHK(hipMemcpy(d_rfp_, hs + b * NWP, n * NWP * 4, hipMemcpyHostToDevice));
-      if (last_fifo_)
-        hipLaunchKernelGGL((orig_reinsert<S, 2>), dim3((unsigned)((n + BS - 1) / BS)), dim3(BS), 0, stream_,
-                           (const u32*)d_rfp_, n, d_table_, table_mask_, (u64)h.seed, (unsigned long long*)d_ctr_);
-      else
-        hipLaunchKernelGGL((orig_reinsert<S, 1>), dim3((unsigned)((n + BS - 1) / BS)), dim3(BS), 0, stream_,
-                           (const u32*)d_rfp_, n, d_table_, 2 * table_mask_ + 1, (u64)h.seed, (unsigned long long*)d_ctr_);
-      HIPCHK(hipGetLastError());
-      HIPCHK(hipStreamSynchronize(stream_));
-    }
-    if (h.total > lb) {
-      if (last_fifo_)
-        hipLaunchKernelGGL((orig_reinsert<S, 2>), dim3((unsigned)((h.total - lb + BS - 1) / BS)), dim3(BS), 0, stream_,
-                           (const u32*)d_states_, (u64)(h.total - lb), d_table_, table_mask_, (u64)h.seed, (unsigned long long*)d_ctr_);
-      else
-        hipLaunchKernelGGL((orig_reinsert<S, 1>), dim3((unsigned)((h.total - lb + BS - 1) / BS)), dim3(BS), 0, stream_,
-                           (const u32*)d_states_, (u64)(h.total - lb), d_table_, 2 * table_mask_ + 1, (u64)h.seed, (unsigned long long*)d_ctr_);
-      HIPCHK(hipGetLastError());
-    }
-    base_ = lb;
-    u64 e = 0;
-    HIPCHK(hipMemcpyAsync(&e, d_ctr_ + K_ERR, 8, hipMemcpyDeviceToHost, stream_));
-    HIPCHK(hipStreamSynchronize(stream_));
-    if (e) { err = "fingerprint table too small for the checkpoint (raise fp_table_bytes)"; return MC_E_OOM; }
-    r.seed = h.seed; r.generated = h.generated; r.distinct = h.distinct; r.depth = h.depth;
-    r.generated_in_model = h.generated_in_model;
-    total_ = h.total; level_begin = h.level_begin; level_count = h.level_count;
+    if (int rc = store_.read_body(in, h.total, h.level_begin, d_rfp_, stage, stream_, d_ctr_ + K_ERR, reinsert, err)) return rc;
+    run_of_ckpt(h, r);
+    level_begin = h.level_begin; level_count = h.level_count;
     return 0;
   }
 
   int dump_states(const std::string& path, std::string& err) override {
-    if (!d_states_) { err = "mc_dump_states before mc_run"; return MC_E_STATE; }
+    if (!store_.states()) { err = "mc_dump_states before mc_run"; return MC_E_STATE; }
     if (unstored_) { err = "mc_dump_states: the last level was counted, not stored (count_final_level)"; return MC_E_STATE; }
-    std::vector<u32> h(total_ * NWP);
-    host_.for_each_segment([&](u64 g0, u64 n, const u32* st, const u64*) { std::memcpy(h.data() + g0 * NWP, st, n * NWP * 4); });
-    HIPCHK(hipMemcpy(h.data() + base_ * NWP, d_states_, (total_ - base_) * NWP * 4, hipMemcpyDeviceToHost));
-    FILE* f = std::fopen(path.c_str(), "w");
-    if (!f) { err = "cannot write " + path; return MC_E_IO; }
-    for (u64 g = 0; g < total_; ++g) {
-      u32 w[NWP];
-      for (int q = 0; q < NWP; ++q) w[q] = h[g * NWP + q];
-      W s; S::unpack(w, s);
-      std::fprintf(f, "%s\n", state_text(s, false).c_str());
-    }
-    std::fclose(f);
-    return 0;
+    return rmc::dump_states<NWP>(store_, path, [&](const u32 (&w)[NWP]) { return words_text(w, false); }, err);
   }
 
   // ================================================================ sharded mode
@@ -2240,21 +2125,21 @@ class OrigGpu : public Backend {
     W s0; S::init(s0);
     u32 w0[S::NW]; S::pack(s0, w0);
     const u64 fp0 = fp64(w0, sres_.seed);
-    total_ = 0; sh_level_begin_ = 0; sh_level_count_ = 0; sh_new_ = 0;
-    base_ = 0; host_.clear();
+    store_.set_total(0); sh_level_begin_ = 0; sh_level_count_ = 0; sh_new_ = 0;
+    store_.reset();
     if ((int)fp_owner(fp0, (u32)world) == rank) {
       u32 wp[NWP] = {0}; for (int q = 0; q < S::NW; ++q) wp[q] = w0[q];
       HIPCHK(hipMemcpy(d_table_ + (fp0 & sh_table_mask()), &fp0, 8, hipMemcpyHostToDevice));
-      HIPCHK(hipMemcpy(d_states_, wp, NWP * 4, hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(store_.states(), wp, NWP * 4, hipMemcpyHostToDevice));
       const u64 nometa = ~0ull;
-      HIPCHK(hipMemcpy(d_meta_, &nometa, 8, hipMemcpyHostToDevice));
-      total_ = 1; sh_level_count_ = 1;
+      HIPCHK(hipMemcpy(store_.meta(), &nometa, 8, hipMemcpyHostToDevice));
+      store_.set_total(1); sh_level_count_ = 1;
     }
     sres_.generated = 1; sres_.distinct = 1; sres_.depth = 1;
     sres_.levels.push_back({1, 0, 0.0});
     if (!S::in_model(s0, m_.rt)) { err = "the initial state violates a state constraint"; return MC_E_UNSUPPORTED; }
     if (S::violated(s0, m_.rt.invariants)) { err = "the initial state violates an invariant"; return MC_E_UNSUPPORTED; }
-    sh_next_write_ = total_;
+    sh_next_write_ = store_.total();
     return 0;
   }
   u64 sh_table_mask() const { return 2 * table_mask_ + 1; }   // sharded seen-set: 8-B entries
@@ -2354,7 +2239,7 @@ class OrigGpu : public Backend {
       const u64 n = (u64)counts[r];
       if (!n) continue;
       MatShArgs m;
-      m.states = d_states_; m.acks = (const u64*)acks + seg_off_ack_[r]; m.n = n; m.chunk_begin = sh_chunk_begin_;
+      m.states = store_.states(); m.acks = (const u64*)acks + seg_off_ack_[r]; m.n = n; m.chunk_begin = sh_chunk_begin_;
       m.chunk_count = sh_chunk_count_; m.out = d_stout_ + seg_off_ack_[r] * (NWP + 4); m.rank_bits = (u64)rank_ << 37;
       m.seed = sres_.seed; m.rt = m_.rt; m.ctr = (unsigned long long*)d_ctr_;
       m.st_states = nullptr; m.st_meta = nullptr; m.st_dst = 0; m.st_cap = 0; m.store = 1;
@@ -2370,7 +2255,7 @@ class OrigGpu : public Backend {
   int shard_store(const void* states, int64_t n, std::string& err) override {
     if (n <= 0) return 0;
     StoreArgs a;
-    a.in = (const u32*)states; a.n = (u64)n; a.dst = sh_next_write_; a.cap = cap_; a.states = d_states_; a.meta = d_meta_;
+    a.in = (const u32*)states; a.n = (u64)n; a.dst = sh_next_write_; a.cap = store_.cap(); a.states = store_.states(); a.meta = store_.meta();
     a.ctr = (unsigned long long*)d_ctr_;
     HIPCHK(hipEventRecord(ev_[0], stream_));
     hipLaunchKernelGGL((orig_store<NWP>), dim3((unsigned)((n + BS - 1) / BS)), dim3(BS), 0, stream_, a);
@@ -2393,7 +2278,7 @@ class OrigGpu : public Backend {
     // the sharded raft_original search is not FIFO-ranked across ranks: any event stops it
     sh_event_ = c[K_EVENT];
     const int kind = sh_event_ == ~0ull ? -1 : (int)(sh_event_ & 3);
-    st[3] = (int64_t)(c[K_ERR] | (sh_next_write_ > cap_ ? (u64)OE_CAP_STORE : 0ull) | (kind == EV_NEXT_ERROR ? (u64)OE_EVAL_LOG_INDEX : 0ull));
+    st[3] = (int64_t)(c[K_ERR] | (sh_next_write_ > store_.cap() ? (u64)OE_CAP_STORE : 0ull) | (kind == EV_NEXT_ERROR ? (u64)OE_EVAL_LOG_INDEX : 0ull));
     st[4] = kind == EV_VIOLATION ? 1 : 0; st[5] = kind == EV_DEADLOCK ? 1 : 0; st[6] = (int64_t)sh_level_count_;
     return 0;
   }
@@ -2425,7 +2310,7 @@ class OrigGpu : public Backend {
     // advance the local level
     sh_level_begin_ += sh_level_count_;
     sh_level_count_ = sh_new_;
-    total_ = sh_next_write_;
+    store_.set_total(sh_next_write_);
     sh_new_ = 0;
     HIPCHK(hipMemset(d_ctr_, 0, K_NCTR * 8));
     HIPCHK(hipMemset(d_ctr_ + K_EVENT, 0xFF, 8));
@@ -2437,7 +2322,7 @@ class OrigGpu : public Backend {
         const u64 key = sh_event_ >> 2, par = key >> 8;
         const int k = (int)(key & 255);
         u32 w[NWP];
-        if (hipMemcpy(w, d_states_ + par * NWP, NWP * 4, hipMemcpyDeviceToHost) == hipSuccess) {
+        if (hipMemcpy(w, store_.states() + par * NWP, NWP * 4, hipMemcpyDeviceToHost) == hipSuccess) {
           W s, t; S::unpack(w, s);
           u64 al[S::AW]; S::all_logs_next(s, al);
           u32 e2 = 0;
@@ -2458,10 +2343,9 @@ class OrigGpu : public Backend {
 
   int shard_read_state(uint64_t gid, std::string& text, uint64_t* meta, std::string& err) const override {
     const u64 local = gid & ((1ull << 37) - 1);
-    if (local >= total_) { err = "shard_read_state: state id outside this rank's store"; return MC_E_INVALID; }
+    if (local >= store_.total()) { err = "shard_read_state: state id outside this rank's store"; return MC_E_INVALID; }
     u32 w[NWP]; u64 m = 0;
-    if (hipMemcpy(w, d_states_ + local * NWP, NWP * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(&m, d_meta_ + local, 8, hipMemcpyDeviceToHost) != hipSuccess) { err = "readback failed"; return MC_E_NO_DEVICE; }
+    if (!store_.read(local, w, &m)) { err = "readback failed"; return MC_E_NO_DEVICE; }
     W s; S::unpack(w, s);
     text = state_text(s, true);
     if (meta) *meta = m;
@@ -2615,8 +2499,8 @@ class OrigGpu : public Backend {
           d.prof = 0;
           NAT_TIMED(2, hipLaunchKernelGGL((orig_dedup_plain<WW, false>), dim3(nblk), dim3(BS), 0, stream_, d));
           MatPlainArgs m;
-          m.states = d_states_; m.meta = d_meta_; m.newrec = d_newrec_; m.base = 0; m.dst_base = sh_next_write_;
-          m.cap = cap_; m.rt = m_.rt; m.ctr = (unsigned long long*)d_ctr_; m.store = last ? 0u : 1u;
+          m.states = store_.states(); m.meta = store_.meta(); m.newrec = d_newrec_; m.base = 0; m.dst_base = sh_next_write_;
+          m.cap = store_.cap(); m.rt = m_.rt; m.ctr = (unsigned long long*)d_ctr_; m.store = last ? 0u : 1u;
           NAT_TIMED(3, hipLaunchKernelGGL((orig_materialize_plain<S>), dim3((unsigned)std::min<u64>(4096, (count * 2 + BS - 1) / BS)),
                                           dim3(BS), 0, stream_, m));
           hipLaunchKernelGGL(orig_advance, dim3(1), dim3(64), 0, stream_, (unsigned long long*)d_ctr_);
@@ -2686,14 +2570,14 @@ class OrigGpu : public Backend {
           for (int r = 0; r < W; ++r) {
             if (!ack[r]) continue;
             MatShArgs m;
-            m.states = d_states_; m.acks = r == me ? d_newrec_ + seg_off_[me] : (const u64*)nat_acks_ + seg_off_ack_[r];
+            m.states = store_.states(); m.acks = r == me ? d_newrec_ + seg_off_[me] : (const u64*)nat_acks_ + seg_off_ack_[r];
             m.n = ack[r]; m.chunk_begin = sh_chunk_begin_;
             m.chunk_count = sh_chunk_count_; m.out = last ? nullptr : d_stout_ + seg_off_ack_[r] * (NWP + 4); m.rank_bits = (u64)me << 37;
             m.seed = sres_.seed; m.rt = m_.rt; m.ctr = (unsigned long long*)d_ctr_;
             m.st_states = nullptr; m.st_meta = nullptr; m.st_dst = 0; m.st_cap = 0; m.store = last ? 0u : 1u;
             if (r == me && !last) {   // my own new states: into my store after the ones of lower ranks
               u64 before = 0; for (int q = 0; q < me; ++q) before += rep[q];
-              m.st_states = d_states_; m.st_meta = d_meta_; m.st_dst = sh_next_write_ + before; m.st_cap = cap_;
+              m.st_states = store_.states(); m.st_meta = store_.meta(); m.st_dst = sh_next_write_ + before; m.st_cap = store_.cap();
             }
             NAT_TIMED(3, hipLaunchKernelGGL((orig_materialize_sh<S>), dim3((unsigned)((ack[r] + BS - 1) / BS)), dim3(BS), 0, stream_, m));
           }
@@ -2715,7 +2599,7 @@ class OrigGpu : public Backend {
             else if (n) {
               StoreArgs a;
               a.in = (const u32*)((const char*)nat_stin_ + in_off * SBW);
-              a.n = n; a.dst = sh_next_write_; a.cap = cap_; a.states = d_states_; a.meta = d_meta_;
+              a.n = n; a.dst = sh_next_write_; a.cap = store_.cap(); a.states = store_.states(); a.meta = store_.meta();
               a.ctr = (unsigned long long*)d_ctr_;
               NAT_TIMED(4, hipLaunchKernelGGL((orig_store<NWP>), dim3((unsigned)((n + BS - 1) / BS)), dim3(BS), 0, stream_, a));
               sres_.kernels[4].algo_bytes += (double)n * (SBW + NWP * 4 + 8);
@@ -2754,7 +2638,7 @@ class OrigGpu : public Backend {
  private:
   OrigModel m_;
   static constexpr int WW = (S::NI + 63) / 64;   // winner-mask words per parent
-  u64* d_table_ = nullptr; u32* d_states_ = nullptr; u64* d_meta_ = nullptr; u64* d_ctr_ = nullptr; u64* d_stop_ = nullptr;
+  u64* d_table_ = nullptr; u64* d_ctr_ = nullptr; u64* d_stop_ = nullptr;
   u64* h_ctr_ = nullptr;     // pinned host copy of the level counters
   bool ctr_clean_ = false;   // d_ctr_ already reset for the next level (queued after the readback)
   u64* d_rfp_ = nullptr; unsigned short* d_rkey_ = nullptr; u32* d_rcnt_blk_ = nullptr; u64* d_newrec_ = nullptr;
@@ -2768,7 +2652,7 @@ class OrigGpu : public Backend {
   u64* d_starter_ = nullptr; u64 starter_cap_ = 0;
   hipStream_t clear_stream_ = nullptr; hipEvent_t clear_ev_ = nullptr;
   u64* run_table_ = nullptr; u64 run_mask_ = 0;   // the table the last single-GPU run ended on (entries - 1)
-  u64 table_mask_ = 0, cap_ = 0, total_ = 0, chunk_states_ = 0;
+  u64 table_mask_ = 0, chunk_states_ = 0;
   u64 unstored_ = 0;   // states of the last level counted but not stored (count_final_level)
   int dev_ = -1, alloc_world_ = 0; uint64_t req_table_ = 0, req_store_ = 0;
   // sharded-mode state
@@ -2792,9 +2676,7 @@ class OrigGpu : public Backend {
   u64 nat_recv_cap_ = 0, nat_acks_cap_ = 0, nat_stin_cap_ = 0;
   std::vector<hipEvent_t> nat_ev_;
   std::vector<hipEvent_t> lvl_ev_;
-  // completed levels moved to host memory: global ids [0, base_) live in host_ (segments)
-  u64 base_ = 0;
-  HostStore host_{NWP};
+  StateStore store_;   // the stored states and parent pointers: device part + host spill
 
   void release_device() override { release(); }
   void release() {
@@ -2805,7 +2687,7 @@ class OrigGpu : public Backend {
     if (ctr_ev_) { (void)hipEventDestroy(ctr_ev_); ctr_ev_ = nullptr; }
     if (d_starter_) { (void)hipFree(d_starter_); d_starter_ = nullptr; starter_cap_ = 0; }
     run_table_ = nullptr; run_mask_ = 0;
-    for (void* p : {(void*)d_table_, (void*)d_states_, (void*)d_meta_, (void*)d_ctr_, (void*)d_stop_, (void*)d_rfp_, (void*)d_rkey_,
+    for (void* p : {(void*)d_table_, (void*)d_ctr_, (void*)d_stop_, (void*)d_rfp_, (void*)d_rkey_,
                     (void*)d_rcnt_blk_, (void*)d_newrec_, (void*)d_winmask_, (void*)d_wcnt_, (void*)d_woff_, (void*)d_urec_, (void*)d_ucnt_,
                     (void*)d_route_, (void*)d_rcnt_, (void*)d_stout_, (void*)d_lead_})
       if (p) (void)hipFree(p);
@@ -2822,7 +2704,8 @@ class OrigGpu : public Backend {
     if (stream_) (void)hipStreamDestroy(stream_);
     if (h_ctr_) (void)hipHostFree(h_ctr_);
     h_ctr_ = nullptr; ctr_clean_ = false;
-    d_table_ = nullptr; d_states_ = nullptr; d_meta_ = nullptr; d_ctr_ = nullptr; d_stop_ = nullptr;
+    store_.release();
+    d_table_ = nullptr; d_ctr_ = nullptr; d_stop_ = nullptr;
     d_rfp_ = nullptr; d_rkey_ = nullptr; d_rcnt_blk_ = nullptr; d_newrec_ = nullptr; d_winmask_ = nullptr; d_wcnt_ = nullptr; d_woff_ = nullptr; d_urec_ = nullptr; d_ucnt_ = nullptr; d_route_ = nullptr; d_rcnt_ = nullptr; d_stout_ = nullptr; stout_cap_ = 0;
     d_lead_ = nullptr;
     stream_ = nullptr; alloc_world_ = 0;
@@ -2835,64 +2718,12 @@ class OrigGpu : public Backend {
     return "?";
   }
 
-  void finish(RunResult& r, std::chrono::steady_clock::time_point t0) {
-    const double M = (double)r.distinct, Ng = (double)r.generated;
-    r.collision_optimistic = M * (Ng - M) / 18446744073709551616.0;
-    r.seconds_total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  }
-
-  // stored state `gid` (global id) and its parent pointer, from the host part or the device
-  bool stored_state(u64 gid, u32 (&w)[NWP], u64& meta) const {
-    if (gid < base_) {
-      std::memcpy(w, host_.state(gid), NWP * 4);
-      meta = host_.meta(gid);
-      return true;
-    }
-    const u64 d = gid - base_;
-    return hipMemcpy(w, d_states_ + d * NWP, NWP * 4, hipMemcpyDeviceToHost) == hipSuccess &&
-           hipMemcpy(&meta, d_meta_ + d, 8, hipMemcpyDeviceToHost) == hipSuccess;
-  }
-
-  // move the completed levels [base_, level_begin) to host memory and the frontier to the
-  // front of the device store (left shift by d in blocks of <= d slots: each block's target
-  // only overlaps blocks already moved)
-  int spill(u64 level_begin, u64 level_count, std::string& err) {
-    const u64 d = level_begin - base_;
-    u32* hs = nullptr; u64* hm = nullptr;
-    const auto ts = std::chrono::steady_clock::now();
-    auto since = [&]() { return std::chrono::duration<double>(std::chrono::steady_clock::now() - ts).count(); };
-    host_.append(d, &hs, &hm);   // a segment of its own: the host part is never reallocated
-    if (progress_) std::fprintf(stderr, "spill: %.1f GB of host memory allocated in %.3f s\n", d * (NWP * 4.0 + 8) / 1e9, since());
-    HIPCHK(hipStreamSynchronize(stream_));
-    HIPCHK(hipMemcpy(hs, d_states_, d * NWP * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(hm, d_meta_, d * 8, hipMemcpyDeviceToHost));
-    if (progress_) std::fprintf(stderr, "spill: copied to host at %.3f s\n", since());
-    for (u64 off = 0; off < level_count; off += d) {
-      const u64 n = std::min<u64>(d, level_count - off);
-      HIPCHK(hipMemcpyAsync(d_states_ + off * NWP, d_states_ + (d + off) * NWP, n * NWP * 4, hipMemcpyDeviceToDevice, stream_));
-      HIPCHK(hipMemcpyAsync(d_meta_ + off, d_meta_ + d + off, n * 8, hipMemcpyDeviceToDevice, stream_));
-      HIPCHK(hipStreamSynchronize(stream_));
-    }
-    base_ = level_begin;
-    return 0;
-  }
-
-  // parent-pointer chase on the host (<= depth device reads of one state each)
+  // a parent pointer: the action in bits 16..23, the parent's global id from bit 24 up
   void build_trace(u64 parent, const char* last_act, const W& last, RunResult& r, std::string& err) {
-    std::vector<std::pair<std::string, std::string>> tr;
-    if (last_act) tr.push_back({last_act, state_text(last, true)});
-    u64 g = parent;
-    while (true) {
-      u32 w[NWP]; u64 meta = 0;
-      if (!stored_state(g, w, meta)) { err = "trace readback failed"; break; }
-      W s; S::unpack(w, s);
-      if (meta == ~0ull) { tr.push_back({"<Initial predicate>", state_text(s, true)}); break; }
-      tr.push_back({kOrigActNames[(meta >> 16) & 0xff], state_text(s, true)});
-      g = meta >> 24;
-    }
-    std::reverse(tr.begin(), tr.end());
-    r.trace = tr;
+    rmc::build_trace<NWP>(store_, parent, last_act, last_act ? state_text(last, true) : std::string(),
+                          [&](const u32 (&w)[NWP]) { return words_text(w, true); }, kOrigActNames, 16, 0xff, 24, r.trace, err);
   }
+  std::string words_text(const u32 (&w)[NWP], bool multiline) const { W s; S::unpack(w, s); return state_text(s, multiline); }
 
   std::string state_text(const W& s, bool multiline) const { return orig_state_text<S>(m_, s, multiline); }
 };
