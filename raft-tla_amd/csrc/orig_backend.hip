@@ -9,7 +9,10 @@
 // fingerprint (16-B entries {fp, ~key}, atomicMax on the complement), i.e. TLC's first-found
 // parent, and every count, parent pointer, counterexample and stop point is TLC's.
 //
-// One BFS level is processed in frontier chunks; each chunk runs on one stream:
+// One BFS level is processed in frontier chunks.  A chunk's kernels run in this order; on the
+// sharded, native and FIFO paths and on small levels all on one stream, on the large levels of the
+// single-GPU -workers N search with step 1 of the next sub-chunk on a second stream beside steps 2-6
+// of this one (run(), "Generate beside dedup"):
 //
 //  1. orig_generate  (compute): one lane per frontier state, a wave-uniform loop over the
 //     action instances; constraint filter, TLC generated counts, out-of-model invariants (TLC
@@ -51,6 +54,7 @@
 
 #include "../../include/raftmc.h"
 #include "backend.h"
+#include "chunk_plan.h"
 #include "fp_gap.h"
 #include "orig_spec.h"
 #include "orig_text.h"
@@ -1031,12 +1035,15 @@ __global__ void __launch_bounds__(BS) orig_materialize(MatArgs a) {
 // and may issue the vector store that zeroes K_CHUNK_NEW before that load has returned — on the
 // GPU the load then sometimes sees the zero and the chunk's new states are lost.  Found when a
 // fourth counter store moved the scalar wait behind the stores.)
-__global__ void orig_advance(unsigned long long* ctr) {
+// rearm_lead = 0: a pipelined level (run(), "generate beside dedup"), whose generate stream re-arms
+// K_LEAD itself -- zeroing it here would wipe the count of the next sub-chunk's orig_generate, which
+// runs beside this kernel.
+__global__ void orig_advance(unsigned long long* ctr, int rearm_lead) {
   if (threadIdx.x == 0) {
     const unsigned long long n = atomicExch(&ctr[K_CHUNK_NEW], 0ull);
     atomicAdd(&ctr[K_LEVEL_NEW], n);
     atomicExch(&ctr[K_INS], 0ull);
-    atomicExch(&ctr[K_LEAD], 0ull);
+    if (rearm_lead) atomicExch(&ctr[K_LEAD], 0ull);
   }
 }
 
@@ -1467,6 +1474,7 @@ class OrigGpu : public Backend {
     if (world == 0) {   // single-GPU run(): the full table's clear runs on a stream of its own beside the first levels
       HIPCHK(hipStreamCreateWithFlags(&clear_stream_, hipStreamNonBlocking));
       HIPCHK(hipEventCreateWithFlags(&clear_ev_, hipEventDisableTiming));
+      HIPCHK(hipEventCreateWithFlags(&gen_ev_, hipEventDisableTiming));
       if (2 * slots >= STARTER_FACTOR * STARTER_SLOTS)
         if (int rc = ensure_starter(STARTER_SLOTS, err)) return rc;
     }
@@ -1483,6 +1491,14 @@ class OrigGpu : public Backend {
   // 4 GiB clear has just ended, and its own clear and orig_migrate's walk (64 MiB each) are the
   // cheapest; 2^24 and 2^25 stay one level longer, 2^26 two, and pay 2x to 8x for both.
   static constexpr u64 STARTER_SLOTS = 1ull << 23, STARTER_FACTOR = 8;
+  // Generate beside dedup: unused dynamic LDS on orig_dedup_plain's launch beside a
+  // generate, so that 4 of its workgroups fit a CU (18.5 KB static + 17.5 KB = 36 KB of 160 KB) instead
+  // of 8.  The dispatcher gives freed wave slots to whatever fits first, and a dedup workgroup (4 x 56
+  // VGPRs) fits long before a generate workgroup (4 x 112): uncapped, the probes take the whole
+  // device and generate advances at a fifth of its speed until they end.  At 4 per CU two generate
+  // waves per SIMD fit beside them.  Measured on C2 (profiles/r08_generate_dedup_overlap_ab.txt):
+  // no pad 23.4-23.8 ms, 6 per CU 23.0, 5 22.6-23.0, 4 22.2-22.7, 3 22.7-22.9; parent 23.3.
+  static constexpr unsigned OVERLAP_DEDUP_PAD_LDS = 17920;
   int ensure_starter(u64 slots, std::string& err) {
     if (d_starter_ && starter_cap_ == slots) return 0;
     if (d_starter_) {
@@ -1506,23 +1522,26 @@ class OrigGpu : public Backend {
     return 0;
   }
 
-  GenArgs gen_args(u64 dev_begin, u64 count, u64 gid0, u64 seed, const RunOpts& o) const {
+  // rec0: the chunk's record buffers start this many parents into the allocations (run()'s pipelined
+  // levels alternate between the two halves, chunk_plan.h; a multiple of BS)
+  GenArgs gen_args(u64 dev_begin, u64 count, u64 gid0, u64 seed, const RunOpts& o, u64 rec0 = 0) const {
     GenArgs g;
     g.states = store_.states(); g.chunk_begin = dev_begin; g.chunk_count = count; g.gid0 = gid0;
-    g.rfp = d_rfp_; g.rkey = d_rkey_; g.rcnt = d_rcnt_blk_; g.seed = seed; g.rt = m_.rt;
+    g.rfp = d_rfp_ + rec0 * S::NI; g.rkey = d_rkey_ + rec0 * S::NI; g.rcnt = d_rcnt_blk_ + rec0 / BS * 4; g.seed = seed; g.rt = m_.rt;
     g.inv_oom = o.inv_out_of_model ? 1u : 0u; g.deadlock = o.check_deadlock ? 1u : 0u;
     g.ctr = (unsigned long long*)d_ctr_;
-    g.lead = d_lead_;
+    g.lead = d_lead_ + rec0;
     return g;
   }
 
   // the successor pass of one chunk: orig_generate over every parent, then orig_generate_lead over
   // the parents with leader work (its grid strides over the count the first kernel left on the
-  // device); K_LEAD must be zero before (level start: orig_reset_ctr, later chunks: orig_advance)
-  void launch_generate(const GenArgs& g, unsigned nblk) {
-    hipLaunchKernelGGL((orig_generate<S>), dim3(nblk), dim3(BS), 0, stream_, g);
+  // device); K_LEAD must be zero before (level start: orig_reset_ctr, later chunks: orig_advance, or
+  // on a pipelined level the generate stream's own re-arm)
+  void launch_generate(const GenArgs& g, unsigned nblk, hipStream_t st) {
+    hipLaunchKernelGGL((orig_generate<S>), dim3(nblk), dim3(BS), 0, st, g);
     const unsigned lblk = std::min<unsigned>(nblk, std::max<unsigned>(64u, nblk / 8));
-    hipLaunchKernelGGL((orig_generate_lead<S>), dim3(lblk), dim3(BS), 0, stream_, g);
+    hipLaunchKernelGGL((orig_generate_lead<S>), dim3(lblk), dim3(BS), 0, st, g);
   }
 
   RouteArgs route_args(u32 world) const {
@@ -1736,6 +1755,13 @@ class OrigGpu : public Backend {
     // counts and checks its states without storing them (an event re-runs FIFO, which stores all)
     const bool count_last = o.count_final_level && !fifo && o.max_depth > 0 && o.checkpoint_path.empty();
     unstored_ = 0;
+    // RAFTMC_OVERLAP_STATES (read per run): the sub-chunk size of a pipelined level; 0 = every level
+    // on one stream, any other value a forced size (whole workgroups) that pipelines every level
+    // with more parents than one sub-chunk.  RAFTMC_OVERLAP_MIN_LEVEL: the smallest pipelined level.
+    const u64 sub_env = env_u64("RAFTMC_OVERLAP_STATES", ~0ull);
+    // (the FIFO path is never split)
+    const ChunkPlan plan(chunk_states_, fifo ? 0 : sub_env == ~0ull ? ChunkPlan::default_sub(chunk_states_) : sub_env,
+                         env_u64("RAFTMC_OVERLAP_MIN_LEVEL", sub_env == ~0ull ? OVERLAP_MIN_LEVEL : 0), BS);
     while (level_count > 0) {
       if (o.max_depth && r.depth >= o.max_depth) { r.left_on_queue = (int64_t)level_count; r.verdict = MC_VERDICT_DEPTH_LIMIT; break; }
       const bool last = count_last && r.depth + 1 >= o.max_depth;
@@ -1781,20 +1807,50 @@ class OrigGpu : public Backend {
       // every chunk's kernels are queued without waiting: the chunk's insert and winner counts
       // stay on the device (grid-stride / scanned offsets), so the host synchronises once per
       // level, for the counters
+      // Generate beside dedup: a large level of the -workers N search is cut into
+      // sub-chunks that alternate between the two halves of the record buffers (chunk_plan.h).
+      // orig_generate + orig_generate_lead of sub-chunk c + 1 (vector ALU) run on clear_stream_ beside
+      // orig_dedup_plain + orig_materialize_plain of sub-chunk c (random HBM probes) on stream_.  All
+      // edges are stream waits on events recorded before the wait is queued (a wait on a
+      // never-recorded event is a no-op); the host still waits once per level:
+      //   first generate of the level  <- gen_ev_: orig_reset_ctr, orig_migrate (and, in stream order
+      //                                   on clear_stream_, the full table's clear)
+      //   dedup(c)                     <- e[1] of c: orig_generate_lead(c) done
+      //   generate(c + 2)              <- e[3] of c: dedup(c) has read the half's records; K_LEAD is
+      //                                   re-armed on the generate stream itself, behind lead(c + 1)
+      //   counter readback             <- stream_ order: the last materialize, which waited for the
+      //                                   last generate, which is behind every earlier one
+      const bool ovl = plan.plan(level_count, chunks_);
+      const int nchunks = (int)chunks_.size();
+      hipStream_t const gst = ovl ? clear_stream_ : stream_;
       int nch = 0;
-      for (u64 cb = level_begin; cb < level_end; cb += chunk_states_, ++nch) {
-        const u64 cnt = std::min<u64>(chunk_states_, level_end - cb);
+      for (; nch < nchunks; ++nch) {
+        const u64 cb = level_begin + chunks_[nch].first, cnt = chunks_[nch].count;
+        const u64 rec0 = chunks_[nch].buffer ? plan.half_cap : 0;
         const unsigned nblk = (unsigned)((cnt + BS - 1) / BS);
         if (int rc = lvl_events(nch)) { err = "hipEventCreate failed"; return rc; }
         hipEvent_t* e = &lvl_ev_[8 * nch];
         // kernels index the device store (global id - store_.base()); keys and parent pointers are global
-        const GenArgs g = gen_args(cb - store_.base(), cnt, cb, r.seed, o);
-        HIPCHK(hipEventRecord(e[0], stream_));
-        launch_generate(g, nblk);
+        const GenArgs g = gen_args(cb - store_.base(), cnt, cb, r.seed, o, rec0);
+        if (ovl && nch == 0) {
+          HIPCHK(hipEventRecord(gen_ev_, stream_));
+          HIPCHK(hipStreamWaitEvent(gst, gen_ev_, 0));
+        }
+        if (ovl && nch >= 2) HIPCHK(hipStreamWaitEvent(gst, lvl_ev_[8 * (nch - 2) + 3], 0));
+        HIPCHK(hipEventRecord(e[0], gst));
+        launch_generate(g, nblk, gst);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(e[1], stream_));
+        HIPCHK(hipEventRecord(e[1], gst));
+        if (ovl) {
+          // K_LEAD for the next sub-chunk's generate, in order behind this one's lead kernel (not
+          // after the level's last: orig_reset_ctr does that, and a late zeroing here could hit the
+          // next level's count)
+          if (nch + 1 < nchunks) HIPCHK(hipMemsetAsync(d_ctr_ + K_LEAD, 0, 8, gst));
+          HIPCHK(hipStreamWaitEvent(stream_, e[1], 0));
+          HIPCHK(hipEventRecord(e[2], stream_));   // dedup's own start: e[1] is the other stream's
+        }
         DedupArgs d;
-        d.rfp = d_rfp_; d.rkey = d_rkey_; d.rcnt = d_rcnt_blk_; d.region = (u64)BS * S::NI; d.gid0 = cb;
+        d.rfp = g.rfp; d.rkey = g.rkey; d.rcnt = g.rcnt; d.region = (u64)BS * S::NI; d.gid0 = cb;
         d.urec = (ulonglong2*)d_urec_; d.ucnt = d_ucnt_;
         d.table = tbl; d.table_mask = tmask; d.newpos = d_newrec_; d.ctr = (unsigned long long*)d_ctr_;
         d.prof = prof_ ? 1u : 0u;
@@ -1805,10 +1861,13 @@ class OrigGpu : public Backend {
           if (count_probes) hipLaunchKernelGGL((orig_probe<true>), dim3(nblk), dim3(BS), 0, stream_, d);
           else hipLaunchKernelGGL((orig_probe<false>), dim3(nblk), dim3(BS), 0, stream_, d);
         } else {
+          // beside a generate (every pipelined sub-chunk but the level's last) the probes run at 4
+          // workgroups per CU, not 8: see OVERLAP_DEDUP_PAD_LDS
+          const unsigned dyn = ovl && nch + 1 < nchunks ? OVERLAP_DEDUP_PAD_LDS : 0u;
           if (count_probes) {
-            hipLaunchKernelGGL((orig_dedup_plain<WW, true>), dim3(nblk), dim3(BS), 0, stream_, d);
+            hipLaunchKernelGGL((orig_dedup_plain<WW, true>), dim3(nblk), dim3(BS), dyn, stream_, d);
           } else {
-            hipLaunchKernelGGL((orig_dedup_plain<WW, false>), dim3(nblk), dim3(BS), 0, stream_, d);
+            hipLaunchKernelGGL((orig_dedup_plain<WW, false>), dim3(nblk), dim3(BS), dyn, stream_, d);
           }
         }
         HIPCHK(hipGetLastError());
@@ -1841,8 +1900,8 @@ class OrigGpu : public Backend {
         HIPCHK(hipEventRecord(e[7], stream_));
         // between chunks; after the level's last chunk the host adds the two counters it reads back
         // anyway (both paths leave the chunk's count in K_CHUNK_NEW: orig_dedup_plain / orig_scan)
-        if (cb + chunk_states_ < level_end) {
-          hipLaunchKernelGGL(orig_advance, dim3(1), dim3(64), 0, stream_, (unsigned long long*)d_ctr_);
+        if (nch + 1 < nchunks) {
+          hipLaunchKernelGGL(orig_advance, dim3(1), dim3(64), 0, stream_, (unsigned long long*)d_ctr_, ovl ? 0 : 1);
           HIPCHK(hipGetLastError());
         }
         for (size_t q = 0; q < r.kernels.size(); ++q) if (fifo || q != 2) r.kernels[q].launches += 1;
@@ -1859,10 +1918,12 @@ class OrigGpu : public Backend {
       HIPCHK(hipEventSynchronize(ctr_ev_));
       double level_ms = 0;
       for (int q = 0; q < nch; ++q) {
-        // event pairs per kernel: generate (e0, e1), dedup (e1, e3), mark/scan (e3, e5; FIFO only),
-        // materialize (e5 or e3, e7)
+        // event pairs per kernel: generate (e0, e1), dedup (e1, e3; e2, e3 on a pipelined level, where
+        // e1 is the generate stream's), mark/scan (e3, e5; FIFO only), materialize (e5 or e3, e7).
+        // On a pipelined level the pairs time kernels that share the device: their sum exceeds the
+        // time the device was busy.
         const hipEvent_t* e = &lvl_ev_[8 * q];
-        const std::pair<int, int> pr[4] = {{0, 1}, {1, 3}, {3, fifo ? 5 : 3}, {fifo ? 5 : 3, 7}};
+        const std::pair<int, int> pr[4] = {{0, 1}, {ovl ? 2 : 1, 3}, {3, fifo ? 5 : 3}, {fifo ? 5 : 3, 7}};
         for (int k = 0; k < 4; ++k) {
           float ms = 0;
           if (pr[k].first != pr[k].second) (void)hipEventElapsedTime(&ms, e[pr[k].first], e[pr[k].second]);
@@ -2163,7 +2224,7 @@ class OrigGpu : public Backend {
       const unsigned nblk = (unsigned)((count + BS - 1) / BS);
       HIPCHK(hipEventRecord(ev_[5], stream_));
       HIPCHK(hipMemsetAsync(d_ctr_ + K_LEAD, 0, 8, stream_));
-      launch_generate(g, nblk);
+      launch_generate(g, nblk, stream_);
       HIPCHK(hipGetLastError());
       HIPCHK(hipEventRecord(ev_[6], stream_));
       hipLaunchKernelGGL(orig_route_blk, dim3(nblk), dim3(BS), 0, stream_, ra);
@@ -2490,7 +2551,7 @@ class OrigGpu : public Backend {
           const GenArgs g = gen_args(sh_chunk_begin_, count, sh_chunk_begin_, sres_.seed, sopts_);
           const unsigned nblk = (unsigned)((count + BS - 1) / BS);
           HIPCHK(hipMemsetAsync(d_ctr_ + K_LEAD, 0, 8, stream_));
-          NAT_TIMED(0, launch_generate(g, nblk));
+          NAT_TIMED(0, launch_generate(g, nblk, stream_));
           sres_.kernels[0].algo_bytes += (double)count * NWP * 4;
           DedupArgs d;
           d.rfp = d_rfp_; d.rkey = d_rkey_; d.rcnt = d_rcnt_blk_; d.region = (u64)BS * S::NI; d.gid0 = sh_chunk_begin_;
@@ -2503,7 +2564,7 @@ class OrigGpu : public Backend {
           m.cap = store_.cap(); m.rt = m_.rt; m.ctr = (unsigned long long*)d_ctr_; m.store = last ? 0u : 1u;
           NAT_TIMED(3, hipLaunchKernelGGL((orig_materialize_plain<S>), dim3((unsigned)std::min<u64>(4096, (count * 2 + BS - 1) / BS)),
                                           dim3(BS), 0, stream_, m));
-          hipLaunchKernelGGL(orig_advance, dim3(1), dim3(64), 0, stream_, (unsigned long long*)d_ctr_);
+          hipLaunchKernelGGL(orig_advance, dim3(1), dim3(64), 0, stream_, (unsigned long long*)d_ctr_, 1);
           HIPCHK(hipGetLastError());
           continue;
         }
@@ -2512,7 +2573,7 @@ class OrigGpu : public Backend {
           const GenArgs g = gen_args(sh_chunk_begin_, count, sh_chunk_begin_, sres_.seed, sopts_);
           const unsigned nblk = (unsigned)((count + BS - 1) / BS);
           HIPCHK(hipMemsetAsync(d_ctr_ + K_LEAD, 0, 8, stream_));
-          NAT_TIMED(0, launch_generate(g, nblk));
+          NAT_TIMED(0, launch_generate(g, nblk, stream_));
           sres_.kernels[0].algo_bytes += (double)count * NWP * 4;
           const RouteArgs ra = route_args((u32)W);
           NAT_TIMED(1, hipLaunchKernelGGL(orig_route_blk, dim3(nblk), dim3(BS), 0, stream_, ra));
@@ -2651,6 +2712,8 @@ class OrigGpu : public Backend {
   // the starter seen-set (ensure_starter) and the stream / event of the full table's clear
   u64* d_starter_ = nullptr; u64 starter_cap_ = 0;
   hipStream_t clear_stream_ = nullptr; hipEvent_t clear_ev_ = nullptr;
+  hipEvent_t gen_ev_ = nullptr;          // pipelined level: stream_ is ready for the level's first generate
+  std::vector<Chunk> chunks_;            // the current level's chunks (chunk_plan.h)
   u64* run_table_ = nullptr; u64 run_mask_ = 0;   // the table the last single-GPU run ended on (entries - 1)
   u64 table_mask_ = 0, chunk_states_ = 0;
   u64 unstored_ = 0;   // states of the last level counted but not stored (count_final_level)
@@ -2684,6 +2747,7 @@ class OrigGpu : public Backend {
     if (clear_stream_) { (void)hipStreamSynchronize(clear_stream_); (void)hipStreamDestroy(clear_stream_); clear_stream_ = nullptr; }
     if (stream_) (void)hipStreamSynchronize(stream_);
     if (clear_ev_) { (void)hipEventDestroy(clear_ev_); clear_ev_ = nullptr; }
+    if (gen_ev_) { (void)hipEventDestroy(gen_ev_); gen_ev_ = nullptr; }
     if (ctr_ev_) { (void)hipEventDestroy(ctr_ev_); ctr_ev_ = nullptr; }
     if (d_starter_) { (void)hipFree(d_starter_); d_starter_ = nullptr; starter_cap_ = 0; }
     run_table_ = nullptr; run_mask_ = 0;
