@@ -1386,6 +1386,10 @@ __global__ void __launch_bounds__(BS) orig_reinsert(const u32* states, u64 n, u6
 
 #include "orig_sim.hip"   // simulation mode: the walker kernel and the host replay of one walk
 
+}  // namespace rmc
+#include "dev_owner.h"   // host only, included here so that the device code above keeps its text
+namespace rmc {
+
 #define HIPCHK(x)                                                                             \
   do {                                                                                        \
     hipError_t e_ = (x);                                                                      \
@@ -1403,8 +1407,7 @@ class OrigGpu : public Backend {
   std::string family() const override { return "raft_original"; }
 
   int observed_collision(double& v, std::string& err) override {
-    if (!d_table_ || alloc_world_ != 0) { err = "after a single-GPU mc_run only"; return MC_E_STATE; }
-    if (!run_table_) { err = "after a single-GPU mc_run only"; return MC_E_STATE; }
+    if (!d_table_ || alloc_world_ != 0 || !run_table_) { err = "after a single-GPU mc_run only"; return MC_E_STATE; }
     // the table the run ended on: the starter, when the model never outgrew it
     return fpgap::observed(run_table_, run_mask_ + 1, last_fifo_ ? 2 : 1, stream_, v, err);
   }
@@ -1448,33 +1451,32 @@ class OrigGpu : public Backend {
     chunk_states_ = (chunk_states_ / BS) * BS;   // whole workgroups: records are grouped per generate workgroup
     const u64 nblk = chunk_states_ / BS, nrec = chunk_states_ * (u64)S::NI;
     table_mask_ = slots - 1;
-    HIPCHK(hipMalloc(&d_table_, slots * 16));
+    HIPCHK(res_.device(&d_table_, slots * 16));
     HIPCHK(store_.alloc(cap, NWP));
-    HIPCHK(hipMalloc(&d_rfp_, nrec * 8));
-    HIPCHK(hipMalloc(&d_rkey_, nrec * 2));
-    HIPCHK(hipMalloc(&d_rcnt_blk_, nblk * 16));
-    HIPCHK(hipMalloc(&d_newrec_, nrec * 8));          // inserted entry positions (single GPU) / replies (sharded)
-    HIPCHK(hipMalloc(&d_urec_, nrec * 16));           // distinct (fp, ~key) per workgroup region
-    HIPCHK(hipMalloc(&d_ucnt_, nblk * 4));
-    HIPCHK(hipMalloc(&d_winmask_, chunk_states_ * WW * 8));
-    HIPCHK(hipMalloc(&d_wcnt_, nblk * 4));
-    HIPCHK(hipMalloc(&d_woff_, nblk * 8));
-    HIPCHK(hipMalloc(&d_lead_, chunk_states_ * 4));
-    HIPCHK(hipMalloc(&d_ctr_, K_NCTR * 8));
-    HIPCHK(hipHostMalloc((void**)&h_ctr_, K_NCTR * 8, hipHostMallocDefault));
-    HIPCHK(hipMalloc(&d_stop_, (1 + OA_NACT) * 8));
+    HIPCHK(res_.device(&d_rfp_, nrec * 8));
+    HIPCHK(res_.device(&d_rkey_, nrec * 2));
+    HIPCHK(res_.device(&d_rcnt_blk_, nblk * 16));
+    HIPCHK(res_.device(&d_newrec_, nrec * 8));          // inserted entry positions (single GPU) / replies (sharded)
+    HIPCHK(res_.device(&d_urec_, nrec * 16));           // distinct (fp, ~key) per workgroup region
+    HIPCHK(res_.device(&d_ucnt_, nblk * 4));
+    HIPCHK(res_.device(&d_winmask_, chunk_states_ * WW * 8));
+    HIPCHK(res_.device(&d_wcnt_, nblk * 4));
+    HIPCHK(res_.device(&d_woff_, nblk * 8));
+    HIPCHK(res_.device(&d_lead_, chunk_states_ * 4));
+    HIPCHK(res_.device(&d_ctr_, K_NCTR * 8));
+    HIPCHK(res_.pinned(&h_ctr_, K_NCTR * 8));
+    HIPCHK(res_.device(&d_stop_, (1 + OA_NACT) * 8));
     HIPCHK(hipMemset(d_winmask_, 0, chunk_states_ * WW * 8));
     if (world >= 1) {   // sharded mode
-      HIPCHK(hipMalloc(&d_route_, (u64)world * nrec * 16));
-      HIPCHK(hipMalloc(&d_rcnt_, 2 * 8 * 8));
+      HIPCHK(res_.device(&d_route_, (u64)world * nrec * 16));
+      HIPCHK(res_.device(&d_rcnt_, 2 * 8 * 8));
     }
-    HIPCHK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
-    for (auto& e : ev_) HIPCHK(hipEventCreate(&e));
-    HIPCHK(hipEventCreateWithFlags(&ctr_ev_, hipEventDisableTiming));
+    HIPCHK(res_.stream(&stream_, hipStreamNonBlocking));
+    HIPCHK(res_.event(&ctr_ev_, hipEventDisableTiming));
     if (world == 0) {   // single-GPU run(): the full table's clear runs on a stream of its own beside the first levels
-      HIPCHK(hipStreamCreateWithFlags(&clear_stream_, hipStreamNonBlocking));
-      HIPCHK(hipEventCreateWithFlags(&clear_ev_, hipEventDisableTiming));
-      HIPCHK(hipEventCreateWithFlags(&gen_ev_, hipEventDisableTiming));
+      HIPCHK(res_.stream(&clear_stream_, hipStreamNonBlocking));
+      HIPCHK(res_.event(&clear_ev_, hipEventDisableTiming));
+      HIPCHK(res_.event(&gen_ev_, hipEventDisableTiming));
       if (2 * slots >= STARTER_FACTOR * STARTER_SLOTS)
         if (int rc = ensure_starter(STARTER_SLOTS, err)) return rc;
     }
@@ -1501,26 +1503,15 @@ class OrigGpu : public Backend {
   static constexpr unsigned OVERLAP_DEDUP_PAD_LDS = 17920;
   int ensure_starter(u64 slots, std::string& err) {
     if (d_starter_ && starter_cap_ == slots) return 0;
-    if (d_starter_) {
-      HIPCHK(hipStreamSynchronize(stream_));
-      HIPCHK(hipFree(d_starter_));
-      d_starter_ = nullptr; starter_cap_ = 0;
-    }
-    HIPCHK(hipMalloc(&d_starter_, slots * 16));
+    if (d_starter_) HIPCHK(hipStreamSynchronize(stream_));
+    starter_cap_ = 0;
+    HIPCHK(res_.device(&d_starter_, slots * 16));   // (frees the old one first)
     starter_cap_ = slots;
     return 0;
   }
 
-  // event pairs (generate, dedup, winners = mark + scan, materialize) of chunk q of the current
-  // level: lvl_ev_[8q .. 8q+8)
-  int lvl_events(int q) {
-    while ((int)lvl_ev_.size() < 8 * (q + 1)) {
-      hipEvent_t e;
-      if (hipEventCreate(&e) != hipSuccess) return MC_E_NO_DEVICE;
-      lvl_ev_.push_back(e);
-    }
-    return 0;
-  }
+  // timing events come from one pool that grows on demand (DevOwner::pool_event); null: the runtime refused one
+  hipEvent_t pool_ev(size_t i) { return (hipEvent_t)res_.pool_event(i); }
 
   // rec0: the chunk's record buffers start this many parents into the allocations (run()'s pipelined
   // levels alternate between the two halves, chunk_plan.h; a multiple of BS)
@@ -1549,6 +1540,167 @@ class OrigGpu : public Backend {
     ra.rfp = d_rfp_; ra.rkey = d_rkey_; ra.rcnt = d_rcnt_blk_; ra.region = (u64)BS * S::NI; ra.route = d_route_;
     ra.route_cap = chunk_states_ * S::NI; ra.world = world; ra.rcnt_out = (unsigned long long*)d_rcnt_;
     return ra;
+  }
+
+  // the seen-set pass over the records g's generate left, against the table the search is on (run()
+  // may be on the starter): orig_merge + orig_probe in FIFO order, orig_dedup_plain otherwise
+  DedupArgs dedup_args(const GenArgs& g, u64 gid0, u64* tbl, u64 tmask) const {
+    DedupArgs d;
+    d.rfp = g.rfp; d.rkey = g.rkey; d.rcnt = g.rcnt; d.region = (u64)BS * S::NI; d.gid0 = gid0;
+    d.urec = (ulonglong2*)d_urec_; d.ucnt = d_ucnt_;
+    d.table = tbl; d.table_mask = tmask; d.newpos = d_newrec_; d.ctr = (unsigned long long*)d_ctr_;
+    d.prof = prof_ ? 1u : 0u;
+    return d;
+  }
+  // dyn: unused dynamic LDS that caps the workgroups per CU (OVERLAP_DEDUP_PAD_LDS)
+  void launch_dedup_plain(const DedupArgs& d, unsigned nblk, unsigned dyn, bool count_probes) {
+    if (count_probes) hipLaunchKernelGGL((orig_dedup_plain<WW, true>), dim3(nblk), dim3(BS), dyn, stream_, d);
+    else hipLaunchKernelGGL((orig_dedup_plain<WW, false>), dim3(nblk), dim3(BS), dyn, stream_, d);
+  }
+
+  // the -workers N store pass: the new states of a chunk of cnt parents, from the positions
+  // orig_dedup_plain left in d_newrec_, behind dst_base (a device slot); store = false: counted
+  // and checked only (count_final_level).  base: global id of device slot 0
+  MatPlainArgs mat_plain_args(u64 base, u64 dst_base, bool store) const {
+    MatPlainArgs m;
+    m.states = store_.states(); m.meta = store_.meta(); m.newrec = d_newrec_; m.base = base; m.dst_base = dst_base;
+    m.cap = store_.cap(); m.rt = m_.rt; m.ctr = (unsigned long long*)d_ctr_; m.store = store ? 1u : 0u;
+    return m;
+  }
+  void launch_materialize_plain(const MatPlainArgs& m, u64 cnt) {
+    hipLaunchKernelGGL((orig_materialize_plain<S>), dim3((unsigned)std::min<u64>(4096, (cnt * 2 + BS - 1) / BS)), dim3(BS), 0, stream_, m);
+  }
+
+  // ---------------------------------------------------------------- sharded stages
+  // What the step API (shard_generate .. shard_store, driven by shard.py) and the native level loop
+  // (shard_run_native) both queue on stream_; neither stage waits for the device.  Each kernel
+  // launch sits in an event pair of its own (timed), read back by harvest() at the caller's next
+  // host synchronisation.
+  struct Seg { const u64* p; u64 n; };   // one rank's segment of an exchange: records, how many
+
+  template <class F>
+  int timed(int k, F&& launch, std::string& err) {
+    const size_t i = pending_.size();
+    hipEvent_t const e0 = pool_ev(2 * i), e1 = pool_ev(2 * i + 1);
+    if (!e0 || !e1) { err = "hipEventCreate failed"; return MC_E_NO_DEVICE; }
+    HIPCHK(hipEventRecord(e0, stream_));
+    launch();
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(e1, stream_));
+    pending_.push_back(k);
+    sres_.kernels[k].launches++;
+    return 0;
+  }
+  void harvest() {
+    for (size_t i = 0; i < pending_.size(); ++i) {
+      float ms = 0;
+      (void)hipEventElapsedTime(&ms, pool_ev(2 * i), pool_ev(2 * i + 1));
+      sres_.kernels[pending_[i]].ms += ms;
+    }
+    pending_.clear();
+  }
+
+  // grow-only device buffer of cap bytes (what it held is not kept)
+  template <class T>
+  int grow(T*& p, u64& cap, u64 need, std::string& err) {
+    if (need <= cap) return 0;
+    if (p) { HIPCHK(hipStreamSynchronize(stream_)); res_.free(&p); }
+    cap = 0;
+    const u64 want = std::max<u64>(need + need / 4, 1 << 20);
+    HIPCHK(res_.device(&p, want));
+    cap = want;
+    return 0;
+  }
+
+  // the chunk sh_chunk_begin_ / sh_chunk_count_ (not empty) of this rank's frontier
+  GenArgs sh_gen_args() const { return gen_args(sh_chunk_begin_, sh_chunk_count_, sh_chunk_begin_, sres_.seed, sopts_); }
+  int stage_generate(const GenArgs& g, unsigned nblk, std::string& err) {
+    HIPCHK(hipMemsetAsync(d_ctr_ + K_LEAD, 0, 8, stream_));
+    if (int rc = timed(0, [&] { launch_generate(g, nblk, stream_); }, err)) return rc;
+    sres_.kernels[0].algo_bytes += (double)sh_chunk_count_ * NWP * 4;
+    return 0;
+  }
+
+  // generate + route of that chunk: the successors' (fp, slot) records bucketed by owner into
+  // d_route_, the per-owner counts in d_rcnt_[0, 8)
+  int stage_generate_route(std::string& err) {
+    HIPCHK(hipMemsetAsync(d_rcnt_, 0, 8 * 8, stream_));
+    if (!sh_chunk_count_) return 0;
+    const unsigned nblk = (unsigned)((sh_chunk_count_ + BS - 1) / BS);
+    if (int rc = stage_generate(sh_gen_args(), nblk, err)) return rc;
+    const RouteArgs ra = route_args((u32)world_);
+    return timed(1, [&] { hipLaunchKernelGGL(orig_route_blk, dim3(nblk), dim3(BS), 0, stream_, ra); }, err);
+  }
+
+  // owner side: the records received from each source rank (seg[r]; at most one chunk's worth in
+  // all) against this rank's seen-set, one launch per non-empty segment; the new ones' slots are
+  // packed at d_newrec_ + seg_off_[r], their counts in d_rcnt_[8, 16)
+  int stage_dedup(const Seg* seg, std::string& err) {
+    HIPCHK(hipMemsetAsync(d_rcnt_ + 8, 0, 8 * 8, stream_));
+    u64 off = 0;
+    for (int r = 0; r < world_; ++r) {
+      seg_off_[r] = off;
+      const u64 n = seg[r].n;
+      if (n) {
+        DedupShArgs d;
+        d.recv = seg[r].p; d.n = n; d.table = d_table_; d.table_mask = sh_table_mask();
+        d.reply = d_newrec_ + off; d.counter = (unsigned long long*)(d_rcnt_ + 8 + r); d.ctr = (unsigned long long*)d_ctr_;
+        if (int rc = timed(2, [&] { hipLaunchKernelGGL(orig_dedup_sh, dim3((unsigned)((n + BS * DEDUP_PER - 1) / (BS * DEDUP_PER))), dim3(BS), 0, stream_, d); }, err))
+          return rc;
+      }
+      off += n;
+    }
+    return 0;
+  }
+
+  // generator side: the acknowledged slots of the current chunk (ack[r]: from owner r) become
+  // states again, invariant-checked and counted per action; packed with their parent pointers at
+  // d_stout_ + seg_off_ack_[r] records for the STATES exchange.  own >= 0: segment `own` is this
+  // rank's, and its states also go straight into the store at own_dst.  last: a counted final
+  // level, nothing is written
+  int stage_rederive(const Seg* ack, bool last, int own, u64 own_dst, std::string& err) {
+    const u64 SBW = (u64)(NWP + 4) * 4;   // STATES record bytes
+    u64 total = 0;
+    for (int r = 0; r < world_; ++r) { seg_off_ack_[r] = total; total += ack[r].n; }
+    if (!last)
+      if (int rc = grow(d_stout_, stout_cap_, total * SBW, err)) return rc;
+    for (int r = 0; r < world_; ++r) {
+      if (!ack[r].n) continue;
+      MatShArgs m;
+      m.states = store_.states(); m.acks = ack[r].p; m.n = ack[r].n; m.chunk_begin = sh_chunk_begin_;
+      m.chunk_count = sh_chunk_count_; m.out = last ? nullptr : d_stout_ + seg_off_ack_[r] * (NWP + 4); m.rank_bits = (u64)rank_ << 37;
+      m.seed = sres_.seed; m.rt = m_.rt; m.ctr = (unsigned long long*)d_ctr_;
+      m.st_states = nullptr; m.st_meta = nullptr; m.st_dst = 0; m.st_cap = 0; m.store = last ? 0u : 1u;
+      if (r == own && !last) { m.st_states = store_.states(); m.st_meta = store_.meta(); m.st_dst = own_dst; m.st_cap = store_.cap(); }
+      if (int rc = timed(3, [&] { hipLaunchKernelGGL((orig_materialize_sh<S>), dim3((unsigned)((m.n + BS - 1) / BS)), dim3(BS), 0, stream_, m); }, err))
+        return rc;
+    }
+    sres_.kernels[3].algo_bytes += (double)total * (8 + NWP * 4 + (last ? 0 : SBW));
+    return 0;
+  }
+
+  // owner side: n received STATES records into the store behind what the level has stored so far
+  int stage_store(const u32* in, u64 n, std::string& err) {
+    StoreArgs a;
+    a.in = in; a.n = n; a.dst = sh_next_write_; a.cap = store_.cap(); a.states = store_.states(); a.meta = store_.meta();
+    a.ctr = (unsigned long long*)d_ctr_;
+    if (int rc = timed(4, [&] { hipLaunchKernelGGL((orig_store<NWP>), dim3((unsigned)((n + BS - 1) / BS)), dim3(BS), 0, stream_, a); }, err))
+      return rc;
+    sres_.kernels[4].algo_bytes += (double)n * ((NWP + 4) * 4 + NWP * 4 + 8);
+    sh_next_write_ += n; sh_new_ += n;
+    return 0;
+  }
+
+  // an empty result of this model: the fingerprint seed and the per-kernel entries of the caller's pipeline
+  static u64 bfs_seed(const RunOpts& o) { return o.seed ? o.seed : 0x5EED5EED2024ull; }
+  static RunResult new_result(u64 seed, std::initializer_list<const char*> kernels) {
+    RunResult r;
+    r.seed = seed;
+    r.state_bytes = NWP * 4;
+    for (int k = 0; k < OA_NACT; ++k) r.action_names.push_back(kOrigActNames[k]);
+    r.act_generated.assign(OA_NACT, 0); r.act_distinct.assign(OA_NACT, 0);
+    for (const char* k : kernels) r.kernels.push_back({k, 0, 0, 0});
+    return r;
   }
 
   // ---------------------------------------------------------------- simulation mode (orig_sim.hip)
@@ -1583,13 +1735,8 @@ class OrigGpu : public Backend {
     const auto t0 = std::chrono::steady_clock::now();
     const u32 depth = sim_depth(o);
     const u64 num = (u64)o.sim_walks, batch = (u64)(o.sim_batch ? o.sim_batch : SIM_DEFAULT_BATCH);
-    r = RunResult();
+    r = new_result(o.seed, {"orig_simulate"});   // (the walks' seed is the caller's, 0 included)
     r.simulated = true;
-    r.seed = o.seed;
-    r.state_bytes = NWP * 4;
-    for (int k = 0; k < OA_NACT; ++k) r.action_names.push_back(kOrigActNames[k]);
-    r.act_generated.assign(OA_NACT, 0); r.act_distinct.assign(OA_NACT, 0);
-    r.kernels = {{"orig_simulate", 0, 0, 0}};
     W s0; S::init(s0);
     r.depth = 1;   // generated: the successors evaluated along the walks (Init is not counted)
     if (!S::in_model(s0, m_.rt)) { err = "the initial state violates a state constraint"; r.verdict = MC_VERDICT_OK; return 0; }
@@ -1600,13 +1747,10 @@ class OrigGpu : public Backend {
       return 0;
     }
     // device counters, freed on every way out
-    struct Dev {
-      unsigned long long* ctr = nullptr; hipEvent_t e0 = nullptr, e1 = nullptr;
-      ~Dev() { if (ctr) (void)hipFree(ctr); if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
-    } d;
-    HIPCHK(hipMalloc(&d.ctr, SK_NCTR * 8));
-    HIPCHK(hipEventCreate(&d.e0));
-    HIPCHK(hipEventCreate(&d.e1));
+    struct Dev { unsigned long long* ctr = nullptr; hipEvent_t e0 = nullptr, e1 = nullptr; DevOwner<HipDevApi> own; } d;
+    HIPCHK(d.own.device(&d.ctr, SK_NCTR * 8));
+    HIPCHK(d.own.event(&d.e0));
+    HIPCHK(d.own.event(&d.e1));
     u64 h[SK_NCTR], event = ~0ull, maxlen = 1;
     for (u64 w0 = 0; w0 < num && event == ~0ull; w0 += batch) {
       const u64 n = std::min<u64>(batch, num - w0);
@@ -1672,336 +1816,83 @@ class OrigGpu : public Backend {
     return 0;
   }
 
+  // ================================================================ the single-GPU search
+  // One run's state, shared by run()'s level loop and its stages below.
+  struct Search {
+    std::chrono::steady_clock::time_point t0;
+    bool fifo = false;           // TLC -workers 1: single-worker FIFO order (16-B {fp, ~key} entries); -workers N: 8-B entries
+    bool count_probes = false;   // count the seen-set probes of the -workers N pipeline (an instrumented kernel)
+    bool count_last = false;     // count_final_level applies to this run
+    u64* tbl = nullptr;          // the table the search is on, and its entry mask
+    u64 tmask = 0, full_mask = 0, st_slots = 0;   // st_slots: the starter's (0: begun on the full table)
+    u64 level_begin = 0, level_count = 1;
+    ChunkPlan plan{0, 0, 0};
+    // the level being expanded: counted not stored, pipelined, its chunks, and what read_level found
+    bool last = false, ovl = false;
+    int nch = 0;
+    u64 nnew = 0;
+    double level_ms = 0;
+    u64 level_end() const { return level_begin + level_count; }
+  };
+
+  // Set up, then per level: spill?, switch to the full table?, queue the level's kernels, read its
+  // counters back (the level's one host wait), decide.
   int run(const RunOpts& o, RunResult& r, std::string& err) override {
     if (o.sim_walks > 0) return simulate(o, r, err);   // TLC -simulate: random walks, not a BFS
     unstored_ = 0;   // a previous run's unstored level must not outlive it (mc_dump_states)
     if (int rc = ensure_alloc(o, 0, err)) return rc;   // world 0 = single-GPU pipeline
-    auto t0 = std::chrono::steady_clock::now();
-    // TLC -workers 1: single-worker FIFO order (16-B {fp, ~key} entries); -workers N: 8-B entries
-    const bool fifo = o.workers == 1;
-    last_fifo_ = fifo;
-    // RAFTMC_COUNT_PROBES: count the seen-set probes of the -workers N pipeline (an instrumented
-    // kernel; read per run, so a caller can count in a run of its own outside a timed region)
-    const bool count_probes = std::getenv("RAFTMC_COUNT_PROBES") != nullptr;
-    const u64 full_mask = fifo ? table_mask_ : 2 * (table_mask_ + 1) - 1;
-    // a run that returned early on the starter may have left the full table's clear in flight
-    HIPCHK(hipStreamSynchronize(clear_stream_));
-    // the starter seen-set (ensure_starter's comment); a recovered search re-inserts every stored
-    // state first, so it starts on the full table
-    u64 st_slots = 0;
-    if (o.recover_path.empty()) {
-      if (full_mask + 1 >= STARTER_FACTOR * STARTER_SLOTS) st_slots = STARTER_SLOTS;
-      if (const char* sv = std::getenv("RAFTMC_STARTER_SLOTS")) {
-        char* end = nullptr;
-        const unsigned long long v = std::strtoull(sv, &end, 0);
-        if (end != sv && *end == 0 && (v & (v - 1)) == 0 && (v == 0 || (v >= 64 && v <= (1ull << 32)))) st_slots = v;
-      }
-    }
-    u64* tbl = d_table_;    // the table the search is on, and its entry mask
-    u64 tmask = full_mask;
-    if (st_slots) {
-      if (int rc = ensure_starter(st_slots, err)) return rc;
-      // the starter's clear first, alone: beside the full clear it gets only its share of the
-      // bandwidth and ends when that one does (measured: 1.03 ms for 256 MiB beside 4 GiB).  The
-      // full clear starts behind it (ctr_ev_ is free until the first level's readback).
-      HIPCHK(hipMemsetAsync(d_starter_, 0, st_slots * (fifo ? 16 : 8), stream_));
-      HIPCHK(hipEventRecord(ctr_ev_, stream_));
-      HIPCHK(hipStreamWaitEvent(clear_stream_, ctr_ev_, 0));
-      HIPCHK(hipMemsetAsync(d_table_, 0, (table_mask_ + 1) * 16, clear_stream_));
-      HIPCHK(hipEventRecord(clear_ev_, clear_stream_));
-      tbl = d_starter_; tmask = st_slots - 1;
-    } else {
-      HIPCHK(hipMemsetAsync(d_table_, 0, (table_mask_ + 1) * 16, stream_));
-      HIPCHK(hipStreamSynchronize(stream_));
-    }
-    run_table_ = tbl; run_mask_ = tmask;
-    ctr_clean_ = false;
-
-    r = RunResult();
-    r.seed = o.seed ? o.seed : 0x5EED5EED2024ull;
-    r.state_bytes = NWP * 4;
-    for (int k = 0; k < OA_NACT; ++k) r.action_names.push_back(kOrigActNames[k]);
-    r.act_generated.assign(OA_NACT, 0); r.act_distinct.assign(OA_NACT, 0);
-    r.kernels = {{"orig_generate", 0, 0, 0}, {"orig_merge_probe", 0, 0, 0}, {"orig_mark_scan", 0, 0, 0}, {"orig_materialize", 0, 0, 0}};
+    Search s;
+    s.t0 = std::chrono::steady_clock::now();
+    s.fifo = o.workers == 1;
+    last_fifo_ = s.fifo;
+    // RAFTMC_COUNT_PROBES: read per run, so a caller can count in a run of its own outside a timed region
+    s.count_probes = std::getenv("RAFTMC_COUNT_PROBES") != nullptr;
+    if (int rc = begin_search(o, s, err)) return rc;
+    r = new_result(bfs_seed(o), {"orig_generate", "orig_merge_probe", "orig_mark_scan", "orig_materialize"});
     store_.reset();
-
-    W s0; S::init(s0);
-    const u64 S_B = NWP * 4;
-    u64 level_begin = 0, level_count = 1;
-    if (!o.recover_path.empty()) {   // TLC -recover: continue the BFS saved by a checkpoint
-      if (int rc = load_checkpoint(o.recover_path, fifo, r, level_begin, level_count, err)) return rc;
-    } else {
-    // ---- Init (raft_original.tla:139-159): one state, generated and distinct
-    u32 w0[S::NW]; S::pack(s0, w0);
-    InitWords<NWP> wp = {}; for (int q = 0; q < S::NW; ++q) wp.w[q] = w0[q];
-    const u64 fp0 = fp64(w0, r.seed);
-    static_assert(NWP <= 64, "orig_init_state: one lane per state word");
-    if (fifo) hipLaunchKernelGGL((orig_init_state<NWP, 2>), dim3(1), dim3(64), 0, stream_, wp, store_.states(), store_.meta(), tbl, tmask, fp0);
-    else hipLaunchKernelGGL((orig_init_state<NWP, 1>), dim3(1), dim3(64), 0, stream_, wp, store_.states(), store_.meta(), tbl, tmask, fp0);
-    HIPCHK(hipGetLastError());
-    r.generated = 1; r.distinct = 1; store_.set_total(1);
-    r.levels.push_back({1, 1, 0.0});
-    r.depth = 1;
-    if (!S::in_model(s0, m_.rt) || S::violated(s0, m_.rt.invariants)) HIPCHK(hipStreamSynchronize(stream_));   // the run ends here
-    if (!S::in_model(s0, m_.rt)) { err = "the initial state violates a state constraint"; r.verdict = MC_VERDICT_OK; r.distinct = 0; return 0; }
-    if (u32 bad = S::violated(s0, m_.rt.invariants)) {
-      r.verdict = MC_VERDICT_INVARIANT_VIOLATION; r.violated = first_violated(bad);
-      r.trace.push_back({"<Initial predicate>", state_text(s0, true)});
-      finish(r, t0); return 0;
-    }
-    }
-
+    bool ended = false;
+    if (int rc = init_level0(o, s, r, ended, err)) return rc;
+    if (ended) return 0;
     // count_final_level: the level at depth max_depth is never expanded, so the -workers N search
     // counts and checks its states without storing them (an event re-runs FIFO, which stores all)
-    const bool count_last = o.count_final_level && !fifo && o.max_depth > 0 && o.checkpoint_path.empty();
+    s.count_last = o.count_final_level && !s.fifo && o.max_depth > 0 && o.checkpoint_path.empty();
     unstored_ = 0;
     // RAFTMC_OVERLAP_STATES (read per run): the sub-chunk size of a pipelined level; 0 = every level
     // on one stream, any other value a forced size (whole workgroups) that pipelines every level
     // with more parents than one sub-chunk.  RAFTMC_OVERLAP_MIN_LEVEL: the smallest pipelined level.
     const u64 sub_env = env_u64("RAFTMC_OVERLAP_STATES", ~0ull);
     // (the FIFO path is never split)
-    const ChunkPlan plan(chunk_states_, fifo ? 0 : sub_env == ~0ull ? ChunkPlan::default_sub(chunk_states_) : sub_env,
-                         env_u64("RAFTMC_OVERLAP_MIN_LEVEL", sub_env == ~0ull ? OVERLAP_MIN_LEVEL : 0), BS);
-    while (level_count > 0) {
-      if (o.max_depth && r.depth >= o.max_depth) { r.left_on_queue = (int64_t)level_count; r.verdict = MC_VERDICT_DEPTH_LIMIT; break; }
-      const bool last = count_last && r.depth + 1 >= o.max_depth;
-      // the device keeps what the search still reads (the frontier) and writes (the next
-      // level); when the next level, predicted from the last growth ratio with a 1.5x margin,
-      // might not fit behind what is stored, the completed levels move to host memory
-      if (level_begin > store_.base() && !last) {
-        const double prev = r.levels.size() >= 2 ? (double)r.levels[r.levels.size() - 2].states : 1.0;
-        const double pred = (double)level_count * std::max(1.0, (double)level_count / std::max(prev, 1.0)) * 1.5;
-        if ((double)(store_.total() - store_.base()) + pred > (double)store_.cap()) {
-          if (progress_) std::fprintf(stderr, "spilling %llu completed states to host memory\n", (unsigned long long)(level_begin - store_.base()));
-          if (int rc = store_.spill(level_begin, level_count, stream_, progress_, err)) return rc;
-        }
-      }
+    s.plan = ChunkPlan(chunk_states_, s.fifo ? 0 : sub_env == ~0ull ? ChunkPlan::default_sub(chunk_states_) : sub_env,
+                       env_u64("RAFTMC_OVERLAP_MIN_LEVEL", sub_env == ~0ull ? OVERLAP_MIN_LEVEL : 0), BS);
+    const u64 S_B = NWP * 4;
+    while (s.level_count > 0) {
+      if (o.max_depth && r.depth >= o.max_depth) { r.left_on_queue = (int64_t)s.level_count; r.verdict = MC_VERDICT_DEPTH_LIMIT; break; }
+      s.last = s.count_last && r.depth + 1 >= o.max_depth;
+      if (int rc = maybe_spill(s, r, err)) return rc;
       if (!ctr_clean_) {
         hipLaunchKernelGGL(orig_reset_ctr, dim3(1), dim3(64), 0, stream_, (unsigned long long*)d_ctr_);
         HIPCHK(hipGetLastError());
       }
       ctr_clean_ = false;
-      const u64 level_end = level_begin + level_count;
-      // The search stays on the starter while the states so far plus all this level can insert
-      // (level_count * NI successors) keep it at most half full, so the starter never reports a
-      // full table.  Otherwise the seen-set moves to the full table before the level is queued:
-      // the stream waits for the clear (no host wait) and orig_migrate re-inserts the entries.
-      if (tbl == d_starter_ && level_end + level_count * (u64)S::NI > st_slots / 2) {
-        HIPCHK(hipStreamWaitEvent(stream_, clear_ev_, 0));
-        unsigned long long* const moved = progress_ ? (unsigned long long*)d_stop_ : nullptr;
-        if (moved) HIPCHK(hipMemsetAsync(d_stop_, 0, 8, stream_));
-        const unsigned mblk = (unsigned)std::min<u64>(2048, (st_slots + BS - 1) / BS);
-        if (fifo) hipLaunchKernelGGL((orig_migrate<2>), dim3(mblk), dim3(BS), 0, stream_, (const u64*)d_starter_, st_slots, d_table_, full_mask, (unsigned long long*)d_ctr_, moved);
-        else hipLaunchKernelGGL((orig_migrate<1>), dim3(mblk), dim3(BS), 0, stream_, (const u64*)d_starter_, st_slots, d_table_, full_mask, (unsigned long long*)d_ctr_, moved);
-        HIPCHK(hipGetLastError());
-        if (moved) {
-          u64 n = 0;
-          HIPCHK(hipMemcpyAsync(&n, d_stop_, 8, hipMemcpyDeviceToHost, stream_));
-          HIPCHK(hipStreamSynchronize(stream_));
-          std::fprintf(stderr, "seen-set switch after level %lld: %llu entries moved from the %llu-slot starter to the full table\n",
-                       (long long)r.depth, (unsigned long long)n, (unsigned long long)st_slots);
-        }
-        tbl = d_table_; tmask = full_mask;
-        run_table_ = tbl; run_mask_ = tmask;
-      }
-      // every chunk's kernels are queued without waiting: the chunk's insert and winner counts
-      // stay on the device (grid-stride / scanned offsets), so the host synchronises once per
-      // level, for the counters
-      // Generate beside dedup: a large level of the -workers N search is cut into
-      // sub-chunks that alternate between the two halves of the record buffers (chunk_plan.h).
-      // orig_generate + orig_generate_lead of sub-chunk c + 1 (vector ALU) run on clear_stream_ beside
-      // orig_dedup_plain + orig_materialize_plain of sub-chunk c (random HBM probes) on stream_.  All
-      // edges are stream waits on events recorded before the wait is queued (a wait on a
-      // never-recorded event is a no-op); the host still waits once per level:
-      //   first generate of the level  <- gen_ev_: orig_reset_ctr, orig_migrate (and, in stream order
-      //                                   on clear_stream_, the full table's clear)
-      //   dedup(c)                     <- e[1] of c: orig_generate_lead(c) done
-      //   generate(c + 2)              <- e[3] of c: dedup(c) has read the half's records; K_LEAD is
-      //                                   re-armed on the generate stream itself, behind lead(c + 1)
-      //   counter readback             <- stream_ order: the last materialize, which waited for the
-      //                                   last generate, which is behind every earlier one
-      const bool ovl = plan.plan(level_count, chunks_);
-      const int nchunks = (int)chunks_.size();
-      hipStream_t const gst = ovl ? clear_stream_ : stream_;
-      int nch = 0;
-      for (; nch < nchunks; ++nch) {
-        const u64 cb = level_begin + chunks_[nch].first, cnt = chunks_[nch].count;
-        const u64 rec0 = chunks_[nch].buffer ? plan.half_cap : 0;
-        const unsigned nblk = (unsigned)((cnt + BS - 1) / BS);
-        if (int rc = lvl_events(nch)) { err = "hipEventCreate failed"; return rc; }
-        hipEvent_t* e = &lvl_ev_[8 * nch];
-        // kernels index the device store (global id - store_.base()); keys and parent pointers are global
-        const GenArgs g = gen_args(cb - store_.base(), cnt, cb, r.seed, o, rec0);
-        if (ovl && nch == 0) {
-          HIPCHK(hipEventRecord(gen_ev_, stream_));
-          HIPCHK(hipStreamWaitEvent(gst, gen_ev_, 0));
-        }
-        if (ovl && nch >= 2) HIPCHK(hipStreamWaitEvent(gst, lvl_ev_[8 * (nch - 2) + 3], 0));
-        HIPCHK(hipEventRecord(e[0], gst));
-        launch_generate(g, nblk, gst);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(e[1], gst));
-        if (ovl) {
-          // K_LEAD for the next sub-chunk's generate, in order behind this one's lead kernel (not
-          // after the level's last: orig_reset_ctr does that, and a late zeroing here could hit the
-          // next level's count)
-          if (nch + 1 < nchunks) HIPCHK(hipMemsetAsync(d_ctr_ + K_LEAD, 0, 8, gst));
-          HIPCHK(hipStreamWaitEvent(stream_, e[1], 0));
-          HIPCHK(hipEventRecord(e[2], stream_));   // dedup's own start: e[1] is the other stream's
-        }
-        DedupArgs d;
-        d.rfp = g.rfp; d.rkey = g.rkey; d.rcnt = g.rcnt; d.region = (u64)BS * S::NI; d.gid0 = cb;
-        d.urec = (ulonglong2*)d_urec_; d.ucnt = d_ucnt_;
-        d.table = tbl; d.table_mask = tmask; d.newpos = d_newrec_; d.ctr = (unsigned long long*)d_ctr_;
-        d.prof = prof_ ? 1u : 0u;
-        // kernel boundaries share an event (each event record costs ~5 us of stream time)
-        if (fifo) {
-          hipLaunchKernelGGL(orig_merge, dim3(nblk), dim3(BS), 0, stream_, d);
-          HIPCHK(hipGetLastError());
-          if (count_probes) hipLaunchKernelGGL((orig_probe<true>), dim3(nblk), dim3(BS), 0, stream_, d);
-          else hipLaunchKernelGGL((orig_probe<false>), dim3(nblk), dim3(BS), 0, stream_, d);
-        } else {
-          // beside a generate (every pipelined sub-chunk but the level's last) the probes run at 4
-          // workgroups per CU, not 8: see OVERLAP_DEDUP_PAD_LDS
-          const unsigned dyn = ovl && nch + 1 < nchunks ? OVERLAP_DEDUP_PAD_LDS : 0u;
-          if (count_probes) {
-            hipLaunchKernelGGL((orig_dedup_plain<WW, true>), dim3(nblk), dim3(BS), dyn, stream_, d);
-          } else {
-            hipLaunchKernelGGL((orig_dedup_plain<WW, false>), dim3(nblk), dim3(BS), dyn, stream_, d);
-          }
-        }
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(e[3], stream_));
-        if (fifo) {
-          MarkArgs mk;
-          mk.newpos = d_newrec_; mk.table = tbl; mk.gid0 = cb; mk.chunk_count = cnt; mk.winmask = d_winmask_;
-          mk.ww = WW; mk.ctr = (unsigned long long*)d_ctr_;
-          hipLaunchKernelGGL(orig_mark, dim3((unsigned)std::min<u64>(2048, (cnt * 2 + BS - 1) / BS)), dim3(BS), 0, stream_, mk);
-          HIPCHK(hipGetLastError());
-          hipLaunchKernelGGL((orig_count<WW>), dim3(nblk), dim3(BS), 0, stream_, (const u64*)d_winmask_, cnt, d_wcnt_);
-          HIPCHK(hipGetLastError());
-          hipLaunchKernelGGL(orig_scan, dim3(1), dim3(SCAN_BS), 0, stream_, (const u32*)d_wcnt_, d_woff_, (u32)nblk, (unsigned long long*)d_ctr_);
-          HIPCHK(hipGetLastError());
-        }
-        if (fifo) HIPCHK(hipEventRecord(e[5], stream_));
-        if (fifo) {
-          MatArgs m;
-          m.states = store_.states(); m.meta = store_.meta(); m.chunk_begin = cb - store_.base(); m.chunk_count = cnt; m.gid0 = cb;
-          m.winmask = d_winmask_; m.woff = d_woff_; m.ww = WW; m.dst_base = level_end - store_.base(); m.cap = store_.cap();
-          m.rt = m_.rt; m.ctr = (unsigned long long*)d_ctr_;
-          hipLaunchKernelGGL((orig_materialize<S>), dim3(nblk), dim3(BS), 0, stream_, m);
-        } else {
-          MatPlainArgs m;
-          m.states = store_.states(); m.meta = store_.meta(); m.newrec = d_newrec_; m.base = store_.base(); m.dst_base = level_end - store_.base();
-          m.cap = store_.cap(); m.rt = m_.rt; m.ctr = (unsigned long long*)d_ctr_; m.store = last ? 0u : 1u;
-          hipLaunchKernelGGL((orig_materialize_plain<S>), dim3((unsigned)std::min<u64>(4096, (cnt * 2 + BS - 1) / BS)), dim3(BS), 0, stream_, m);
-        }
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(e[7], stream_));
-        // between chunks; after the level's last chunk the host adds the two counters it reads back
-        // anyway (both paths leave the chunk's count in K_CHUNK_NEW: orig_dedup_plain / orig_scan)
-        if (nch + 1 < nchunks) {
-          hipLaunchKernelGGL(orig_advance, dim3(1), dim3(64), 0, stream_, (unsigned long long*)d_ctr_, ovl ? 0 : 1);
-          HIPCHK(hipGetLastError());
-        }
-        for (size_t q = 0; q < r.kernels.size(); ++q) if (fifo || q != 2) r.kernels[q].launches += 1;
-        r.kernels[0].algo_bytes += (double)cnt * S_B;        // + G_in * 10 record bytes per level below
-      }
-      u64* const c = h_ctr_;   // pinned: the readback is one direct copy
-      HIPCHK(hipMemcpyAsync(c, d_ctr_, K_NCTR * 8, hipMemcpyDeviceToHost, stream_));
-      HIPCHK(hipEventRecord(ctr_ev_, stream_));
-      hipLaunchKernelGGL(orig_reset_ctr, dim3(1), dim3(64), 0, stream_, (unsigned long long*)d_ctr_);
-      HIPCHK(hipGetLastError());
-      ctr_clean_ = true;
-      // the host waits for the copy alone (the level's kernel events were all recorded before it):
-      // the reset behind it runs while the host looks at the counters
-      HIPCHK(hipEventSynchronize(ctr_ev_));
-      double level_ms = 0;
-      for (int q = 0; q < nch; ++q) {
-        // event pairs per kernel: generate (e0, e1), dedup (e1, e3; e2, e3 on a pipelined level, where
-        // e1 is the generate stream's), mark/scan (e3, e5; FIFO only), materialize (e5 or e3, e7).
-        // On a pipelined level the pairs time kernels that share the device: their sum exceeds the
-        // time the device was busy.
-        const hipEvent_t* e = &lvl_ev_[8 * q];
-        const std::pair<int, int> pr[4] = {{0, 1}, {ovl ? 2 : 1, 3}, {3, fifo ? 5 : 3}, {fifo ? 5 : 3, 7}};
-        for (int k = 0; k < 4; ++k) {
-          float ms = 0;
-          if (pr[k].first != pr[k].second) (void)hipEventElapsedTime(&ms, e[pr[k].first], e[pr[k].second]);
-          r.kernels[k].ms += ms; level_ms += ms;
-        }
-      }
-      const u64 nnew = c[K_LEVEL_NEW] + c[K_CHUNK_NEW];   // earlier chunks (orig_advance) + the last one
-      const u64 next_write = level_end + nnew;
-      if (progress_)   // TLC's progress line, per BFS level (RAFTMC_PROGRESS=1), on stderr
-        std::fprintf(stderr, "Progress(%lld) at %.3f s: %lld states generated, %llu distinct states found, %llu states left on queue "
-                             "(level kernels %.1f ms, %d chunk(s), store %llu/%llu, %llu on the host%s)\n",
-                     (long long)r.depth + 1,
-                     std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(),
-                     (long long)(r.generated + (int64_t)[&] { u64 g = 0; for (int k = 0; k < OA_NACT; ++k) g += c[K_ACT + k]; return g; }()),
-                     (unsigned long long)(level_end + nnew), (unsigned long long)nnew, level_ms, nch,
-                     (unsigned long long)((last ? level_end : next_write) - store_.base()), (unsigned long long)store_.cap(), (unsigned long long)store_.base(),
-                     last ? "; the last level counted, not stored" : "");
-      if (progress_ && (c[K_EVENT] != ~0ull || c[K_ERR]))
-        std::fprintf(stderr, "level %lld: event word 0x%llx, error flags 0x%llx\n", (long long)r.depth + 1,
-                     (unsigned long long)c[K_EVENT], (unsigned long long)c[K_ERR]);
-      if (prof_) {
-        for (int q = 0; q < 4; ++q) prof_acc_[q] += c[K_PROF + q];
-        prof_acc_[4] = std::max<u64>(prof_acc_[4], c[K_PROF + 5]);
-      }
-      const u64 G_in = c[K_GEN_IN];
-      // per-kernel algorithmic bytes: generate writes 10-B records; dedup reads them and probes
-      // (8 B per in-model successor) and writes 16 B per new state; mark reads the
-      // inserted positions + keys and sets winner bits; materialize re-reads the parent and writes
-      // state + parent pointer
-      r.kernels[0].algo_bytes += (double)G_in * 10;
-      r.kernels[1].algo_bytes += (double)G_in * (10 + 8) + (double)nnew * (16 + 8);
-      r.kernels[2].algo_bytes += (double)nnew * (8 + 16 + 8);
-      r.kernels[3].algo_bytes += (double)level_count * WW * 8 + (double)nnew * (S_B + S_B + 8);
-      r.seconds_kernels += level_ms / 1000.0;
-      r.n_launches += 1;
-      if (!last && next_write - store_.base() > store_.cap()) c[K_ERR] |= OE_CAP_STORE;
-      if (c[K_EVENT] != ~0ull && !fifo && (c[K_ERR] & ~(u64)OE_CAP_STORE) == 0) {
-        // TLC -workers N found an event: TLC's counterexample and stop point are the single-worker
-        // search's, so the model is searched again in FIFO order (it stops at this level)
-        RunOpts o1 = o;
-        o1.workers = 1;
-        o1.recover_path.clear();        // a checkpoint of this search is in its order, not TLC's: start over
-        o1.checkpoint_path.clear();
-        const u64 evw = c[K_EVENT];
-        const int64_t ev_depth = r.depth + 1;
-        const int rc = run(o1, r, err);
-        if (rc == 0 && r.verdict == MC_VERDICT_CAPACITY_OVERFLOW) {
-          // the FIFO re-search stores every level (count_final_level included): when it does not
-          // fit, the event the -workers N pass found is still reported, not lost
-          static const char* const kind[4] = {"an evaluation error", "a deadlock", "an invariant evaluation error", "an invariant violation"};
-          r.error = std::string("the -workers N search found ") + kind[evw & 3] + " at depth " + std::to_string(ev_depth) +
-                    "; TLC's single-worker re-search of it (for TLC's counterexample and stop point) ran out of capacity: " + r.error;
-        }
-        return rc;
-      }
-      if (c[K_EVENT] != ~0ull && (c[K_ERR] & ~(u64)OE_CAP_STORE) == 0) {
+      if (int rc = maybe_switch_to_full_table(s, r, err)) return rc;
+      if (int rc = queue_level(o, s, r, err)) return rc;
+      if (int rc = read_level(s, r, err)) return rc;
+      u64* const c = h_ctr_;
+      const u64 level_end = s.level_end(), nnew = s.nnew;
+      if (!s.last && level_end + nnew - store_.base() > store_.cap()) c[K_ERR] |= OE_CAP_STORE;
+      const bool event = c[K_EVENT] != ~0ull && (c[K_ERR] & ~(u64)OE_CAP_STORE) == 0;
+      if (event && !s.fifo) return research_fifo(o, c[K_EVENT], r, err);
+      if (event) {
         // the level's first event in TLC's order stops the search; a full state store only
         // matters when it cut off states that come before the event in key order
         const u64 stored = std::min<u64>(nnew, store_.cap() - std::min<u64>(store_.cap(), level_end - store_.base()));
         bool decided = false;
-        if (int rc = handle_event(c[K_EVENT], level_begin, level_count, nnew, stored, r, decided, err)) return rc;
+        if (int rc = handle_event(c[K_EVENT], s.level_begin, s.level_count, nnew, stored, r, decided, err)) return rc;
         if (decided) { store_.set_total(level_end + stored); break; }
       }
       if (c[K_ERR]) {
-        const u64 e = c[K_ERR];
         r.verdict = MC_VERDICT_CAPACITY_OVERFLOW;
-        std::ostringstream os;
-        os << "error flags 0x" << std::hex << e << std::dec << " while expanding state " << (c[K_ERRGID] ? (int64_t)(c[K_ERRGID] - 1) : -1) << ":";
-        if (e & OE_CAP_ELECTIONS) os << " elections set exceeds the compiled capacity;";
-        if (e & OE_CAP_COUNT) os << " message count / bag capacity exceeded;";
-        if (e & OE_CAP_STORE)
-          os << " state store full (raise state_store_bytes): " << store_.cap() << " state slots, " << store_.base()
-             << " states on the host, level ends at " << level_end << ", " << nnew << " new;";
-        if (e & OE_TABLE_FULL) os << " fingerprint table full (raise fp_table_bytes);";
-        // the summary counts the completed levels (their sizes sum to it, and the depth is theirs);
-        // whatever part of the interrupted level reached the store is not a level of the search
-        os << " the summary counts the " << level_end << " states of the " << r.depth << " completed levels;";
-        r.error = os.str();
+        r.error = capacity_error(c, level_end, nnew, r.depth);
         store_.set_total(level_end);
         r.distinct = (int64_t)level_end;
         break;
@@ -2009,27 +1900,326 @@ class OrigGpu : public Backend {
       int64_t gen = 0;
       for (int k = 0; k < OA_NACT; ++k) { r.act_generated[k] += (int64_t)c[K_ACT + k]; r.act_distinct[k] += (int64_t)c[K_ACT + OA_NACT + k]; gen += (int64_t)c[K_ACT + k]; }
       r.generated += gen;
-      r.generated_in_model += (int64_t)G_in;
+      r.generated_in_model += (int64_t)c[K_GEN_IN];
       r.seen_set_probes += (int64_t)c[K_PROBES];
-      r.algo_bytes += (double)level_count * S_B + (double)G_in * 8 + (double)nnew * (16 + S_B);
-      if (last) unstored_ = nnew;   // counted, not in the store (the store's total counts stored states)
+      r.algo_bytes += (double)s.level_count * S_B + (double)c[K_GEN_IN] * 8 + (double)nnew * (16 + S_B);
+      if (s.last) unstored_ = nnew;   // counted, not in the store (the store's total counts stored states)
       else store_.set_total(store_.total() + nnew);
       r.distinct = (int64_t)(store_.total() + unstored_);
       r.levels.back().generated = gen;
-      r.levels.back().kernel_ms = level_ms;
+      r.levels.back().kernel_ms = s.level_ms;
       if (nnew > 0) { r.levels.push_back({(int64_t)nnew, 0, 0.0}); r.depth += 1; }
-      level_begin += level_count;
-      level_count = nnew;
-      if (o.checkpoint_every > 0 && !o.checkpoint_path.empty() && r.depth % o.checkpoint_every == 0 && level_count > 0)
-        if (int rc = save_checkpoint(o.checkpoint_path, r, level_begin, level_count, err)) return rc;
+      s.level_begin += s.level_count;
+      s.level_count = nnew;
+      if (o.checkpoint_every > 0 && !o.checkpoint_path.empty() && r.depth % o.checkpoint_every == 0 && s.level_count > 0)
+        if (int rc = save_checkpoint(o.checkpoint_path, r, s.level_begin, s.level_count, err)) return rc;
     }
     if (prof_ && prof_acc_[3])
       std::fprintf(stderr, "orig_probe per workgroup (us): %.2f  (%llu workgroups)\n",
                    prof_acc_[1] / 100.0 / prof_acc_[3], (unsigned long long)prof_acc_[3]);
     if (prof_) std::fprintf(stderr, "max concurrent dedup workgroups %llu\n", (unsigned long long)prof_acc_[4]);
     for (auto& x : prof_acc_) x = 0;
-    finish(r, t0);
+    finish(r, s.t0);
     return 0;
+  }
+
+  // The seen-set the search begins on, cleared: the starter (ensure_starter's comment) with the
+  // full table's clear queued beside it, or the full table; a recovered search re-inserts every
+  // stored state first, so it starts on the full table.
+  int begin_search(const RunOpts& o, Search& s, std::string& err) {
+    s.full_mask = s.fifo ? table_mask_ : 2 * (table_mask_ + 1) - 1;
+    // a run that returned early on the starter may have left the full table's clear in flight
+    HIPCHK(hipStreamSynchronize(clear_stream_));
+    if (o.recover_path.empty()) {
+      if (s.full_mask + 1 >= STARTER_FACTOR * STARTER_SLOTS) s.st_slots = STARTER_SLOTS;
+      if (const char* sv = std::getenv("RAFTMC_STARTER_SLOTS")) {
+        char* end = nullptr;
+        const unsigned long long v = std::strtoull(sv, &end, 0);
+        if (end != sv && *end == 0 && (v & (v - 1)) == 0 && (v == 0 || (v >= 64 && v <= (1ull << 32)))) s.st_slots = v;
+      }
+    }
+    s.tbl = d_table_; s.tmask = s.full_mask;
+    if (s.st_slots) {
+      if (int rc = ensure_starter(s.st_slots, err)) return rc;
+      // the starter's clear first, alone: beside the full clear it gets only its share of the
+      // bandwidth and ends when that one does (measured: 1.03 ms for 256 MiB beside 4 GiB).  The
+      // full clear starts behind it (ctr_ev_ is free until the first level's readback).
+      HIPCHK(hipMemsetAsync(d_starter_, 0, s.st_slots * (s.fifo ? 16 : 8), stream_));
+      HIPCHK(hipEventRecord(ctr_ev_, stream_));
+      HIPCHK(hipStreamWaitEvent(clear_stream_, ctr_ev_, 0));
+      HIPCHK(hipMemsetAsync(d_table_, 0, (table_mask_ + 1) * 16, clear_stream_));
+      HIPCHK(hipEventRecord(clear_ev_, clear_stream_));
+      s.tbl = d_starter_; s.tmask = s.st_slots - 1;
+    } else {
+      HIPCHK(hipMemsetAsync(d_table_, 0, (table_mask_ + 1) * 16, stream_));
+      HIPCHK(hipStreamSynchronize(stream_));
+    }
+    run_table_ = s.tbl; run_mask_ = s.tmask;
+    ctr_clean_ = false;
+    return 0;
+  }
+
+  // Level 0: the checkpoint's frontier (TLC -recover), or Init (raft_original.tla:139-159), one
+  // state, generated and distinct.  ended: Init is outside the model or violates an invariant.
+  int init_level0(const RunOpts& o, Search& s, RunResult& r, bool& ended, std::string& err) {
+    if (!o.recover_path.empty()) return load_checkpoint(o.recover_path, s.fifo, r, s.level_begin, s.level_count, err);
+    W s0; S::init(s0);
+    u32 w0[S::NW]; S::pack(s0, w0);
+    InitWords<NWP> wp = {}; for (int q = 0; q < S::NW; ++q) wp.w[q] = w0[q];
+    const u64 fp0 = fp64(w0, r.seed);
+    static_assert(NWP <= 64, "orig_init_state: one lane per state word");
+    if (s.fifo) hipLaunchKernelGGL((orig_init_state<NWP, 2>), dim3(1), dim3(64), 0, stream_, wp, store_.states(), store_.meta(), s.tbl, s.tmask, fp0);
+    else hipLaunchKernelGGL((orig_init_state<NWP, 1>), dim3(1), dim3(64), 0, stream_, wp, store_.states(), store_.meta(), s.tbl, s.tmask, fp0);
+    HIPCHK(hipGetLastError());
+    r.generated = 1; r.distinct = 1; store_.set_total(1);
+    r.levels.push_back({1, 1, 0.0});
+    r.depth = 1;
+    const u32 bad = S::violated(s0, m_.rt.invariants);
+    ended = !S::in_model(s0, m_.rt) || bad;
+    if (ended) HIPCHK(hipStreamSynchronize(stream_));   // the run ends here
+    if (!S::in_model(s0, m_.rt)) { err = "the initial state violates a state constraint"; r.verdict = MC_VERDICT_OK; r.distinct = 0; return 0; }
+    if (bad) {
+      r.verdict = MC_VERDICT_INVARIANT_VIOLATION; r.violated = first_violated(bad);
+      r.trace.push_back({"<Initial predicate>", state_text(s0, true)});
+      finish(r, s.t0);
+    }
+    return 0;
+  }
+
+  // The device keeps what the search still reads (the frontier) and writes (the next level);
+  // when the next level, predicted from the last growth ratio with a 1.5x margin, might not fit
+  // behind what is stored, the completed levels move to host memory.
+  int maybe_spill(const Search& s, const RunResult& r, std::string& err) {
+    if (s.level_begin <= store_.base() || s.last) return 0;
+    const double prev = r.levels.size() >= 2 ? (double)r.levels[r.levels.size() - 2].states : 1.0;
+    const double pred = (double)s.level_count * std::max(1.0, (double)s.level_count / std::max(prev, 1.0)) * 1.5;
+    if ((double)(store_.total() - store_.base()) + pred <= (double)store_.cap()) return 0;
+    if (progress_) std::fprintf(stderr, "spilling %llu completed states to host memory\n", (unsigned long long)(s.level_begin - store_.base()));
+    return store_.spill(s.level_begin, s.level_count, stream_, progress_, err);
+  }
+
+  // The search stays on the starter while the states so far plus all this level can insert
+  // (level_count * NI successors) keep it at most half full, so the starter never reports a
+  // full table.  Otherwise the seen-set moves to the full table before the level is queued:
+  // the stream waits for the clear (no host wait) and orig_migrate re-inserts the entries.
+  int maybe_switch_to_full_table(Search& s, const RunResult& r, std::string& err) {
+    if (s.tbl != d_starter_ || s.level_end() + s.level_count * (u64)S::NI <= s.st_slots / 2) return 0;
+    HIPCHK(hipStreamWaitEvent(stream_, clear_ev_, 0));
+    unsigned long long* const moved = progress_ ? (unsigned long long*)d_stop_ : nullptr;
+    if (moved) HIPCHK(hipMemsetAsync(d_stop_, 0, 8, stream_));
+    const unsigned mblk = (unsigned)std::min<u64>(2048, (s.st_slots + BS - 1) / BS);
+    if (s.fifo) hipLaunchKernelGGL((orig_migrate<2>), dim3(mblk), dim3(BS), 0, stream_, (const u64*)d_starter_, s.st_slots, d_table_, s.full_mask, (unsigned long long*)d_ctr_, moved);
+    else hipLaunchKernelGGL((orig_migrate<1>), dim3(mblk), dim3(BS), 0, stream_, (const u64*)d_starter_, s.st_slots, d_table_, s.full_mask, (unsigned long long*)d_ctr_, moved);
+    HIPCHK(hipGetLastError());
+    if (moved) {
+      u64 n = 0;
+      HIPCHK(hipMemcpyAsync(&n, d_stop_, 8, hipMemcpyDeviceToHost, stream_));
+      HIPCHK(hipStreamSynchronize(stream_));
+      std::fprintf(stderr, "seen-set switch after level %lld: %llu entries moved from the %llu-slot starter to the full table\n",
+                   (long long)r.depth, (unsigned long long)n, (unsigned long long)s.st_slots);
+    }
+    s.tbl = d_table_; s.tmask = s.full_mask;
+    run_table_ = s.tbl; run_mask_ = s.tmask;
+    return 0;
+  }
+
+  // Every chunk's kernels are queued without waiting: the chunk's insert and winner counts stay on
+  // the device (grid-stride / scanned offsets), so the host synchronises once per level, for the
+  // counters (read_level).  Chunk q of the level uses the pool's events 8q .. 8q+7: generate
+  // (e0, e1), the seen-set pass (e1 or e2, e3), mark + scan (e3, e5; FIFO only), materialize (e5
+  // or e3, e7); kernel boundaries share an event (each event record costs ~5 us of stream time).
+  //
+  // Generate beside dedup: a large level of the -workers N search is cut into
+  // sub-chunks that alternate between the two halves of the record buffers (chunk_plan.h).
+  // orig_generate + orig_generate_lead of sub-chunk c + 1 (vector ALU) run on clear_stream_ beside
+  // orig_dedup_plain + orig_materialize_plain of sub-chunk c (random HBM probes) on stream_.  All
+  // edges are stream waits on events recorded before the wait is queued (a wait on a
+  // never-recorded event is a no-op); the host still waits once per level:
+  //   first generate of the level  <- gen_ev_: orig_reset_ctr, orig_migrate (and, in stream order
+  //                                   on clear_stream_, the full table's clear)
+  //   dedup(c)                     <- e[1] of c: orig_generate_lead(c) done
+  //   generate(c + 2)              <- e[3] of c: dedup(c) has read the half's records; K_LEAD is
+  //                                   re-armed on the generate stream itself, behind lead(c + 1)
+  //   counter readback             <- stream_ order: the last materialize, which waited for the
+  //                                   last generate, which is behind every earlier one
+  int queue_level(const RunOpts& o, Search& s, RunResult& r, std::string& err) {
+    s.ovl = s.plan.plan(s.level_count, chunks_);
+    const int nchunks = (int)chunks_.size();
+    hipStream_t const gst = s.ovl ? clear_stream_ : stream_;
+    for (s.nch = 0; s.nch < nchunks; ++s.nch) {
+      const int q = s.nch;
+      const u64 cb = s.level_begin + chunks_[q].first, cnt = chunks_[q].count;
+      const u64 rec0 = chunks_[q].buffer ? s.plan.half_cap : 0;
+      const unsigned nblk = (unsigned)((cnt + BS - 1) / BS);
+      hipEvent_t e[8];
+      for (int j = 0; j < 8; ++j) e[j] = pool_ev(8 * q + j);
+      if (!e[7]) { err = "hipEventCreate failed"; return MC_E_NO_DEVICE; }
+      // kernels index the device store (global id - store_.base()); keys and parent pointers are global
+      const GenArgs g = gen_args(cb - store_.base(), cnt, cb, r.seed, o, rec0);
+      if (s.ovl && q == 0) {
+        HIPCHK(hipEventRecord(gen_ev_, stream_));
+        HIPCHK(hipStreamWaitEvent(gst, gen_ev_, 0));
+      }
+      if (s.ovl && q >= 2) HIPCHK(hipStreamWaitEvent(gst, pool_ev(8 * (q - 2) + 3), 0));
+      HIPCHK(hipEventRecord(e[0], gst));
+      launch_generate(g, nblk, gst);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipEventRecord(e[1], gst));
+      if (s.ovl) {
+        // K_LEAD for the next sub-chunk's generate, in order behind this one's lead kernel (not
+        // after the level's last: orig_reset_ctr does that, and a late zeroing here could hit the
+        // next level's count)
+        if (q + 1 < nchunks) HIPCHK(hipMemsetAsync(d_ctr_ + K_LEAD, 0, 8, gst));
+        HIPCHK(hipStreamWaitEvent(stream_, e[1], 0));
+        HIPCHK(hipEventRecord(e[2], stream_));   // dedup's own start: e[1] is the other stream's
+      }
+      // the seen-set pass, then the store pass: each one sequence per search order.  Beside a generate
+      // (every pipelined sub-chunk but the level's last) the -workers N probes run at 4 workgroups per
+      // CU, not 8: see OVERLAP_DEDUP_PAD_LDS
+      const DedupArgs d = dedup_args(g, cb, s.tbl, s.tmask);
+      if (s.fifo) { if (int rc = queue_merge_probe(s, d, nblk, err)) return rc; }
+      else launch_dedup_plain(d, nblk, s.ovl && q + 1 < nchunks ? OVERLAP_DEDUP_PAD_LDS : 0u, s.count_probes);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipEventRecord(e[3], stream_));
+      if (s.fifo) { if (int rc = queue_winners_materialize(s, cb, cnt, nblk, e[5], err)) return rc; }
+      else launch_materialize_plain(mat_plain_args(store_.base(), s.level_end() - store_.base(), !s.last), cnt);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipEventRecord(e[7], stream_));
+      // between chunks; after the level's last chunk the host adds the two counters it reads back
+      // anyway (both paths leave the chunk's count in K_CHUNK_NEW: orig_dedup_plain / orig_scan)
+      if (q + 1 < nchunks) {
+        hipLaunchKernelGGL(orig_advance, dim3(1), dim3(64), 0, stream_, (unsigned long long*)d_ctr_, s.ovl ? 0 : 1);
+        HIPCHK(hipGetLastError());
+      }
+      for (size_t k = 0; k < r.kernels.size(); ++k) if (s.fifo || k != 2) r.kernels[k].launches += 1;
+      r.kernels[0].algo_bytes += (double)cnt * NWP * 4;        // + G_in * 10 record bytes per level (read_level)
+    }
+    return 0;
+  }
+
+  // a chunk's seen-set pass in TLC's single-worker order: the records merged per workgroup, then probed
+  int queue_merge_probe(const Search& s, const DedupArgs& d, unsigned nblk, std::string& err) {
+    hipLaunchKernelGGL(orig_merge, dim3(nblk), dim3(BS), 0, stream_, d);
+    HIPCHK(hipGetLastError());
+    if (s.count_probes) hipLaunchKernelGGL((orig_probe<true>), dim3(nblk), dim3(BS), 0, stream_, d);
+    else hipLaunchKernelGGL((orig_probe<false>), dim3(nblk), dim3(BS), 0, stream_, d);
+    return 0;
+  }
+
+  // its store pass: the winners among the inserted records (mark, count, scan; e5 behind them),
+  // then their states in key order
+  int queue_winners_materialize(const Search& s, u64 cb, u64 cnt, unsigned nblk, hipEvent_t e5, std::string& err) {
+    MarkArgs mk;
+    mk.newpos = d_newrec_; mk.table = s.tbl; mk.gid0 = cb; mk.chunk_count = cnt; mk.winmask = d_winmask_;
+    mk.ww = WW; mk.ctr = (unsigned long long*)d_ctr_;
+    hipLaunchKernelGGL(orig_mark, dim3((unsigned)std::min<u64>(2048, (cnt * 2 + BS - 1) / BS)), dim3(BS), 0, stream_, mk);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL((orig_count<WW>), dim3(nblk), dim3(BS), 0, stream_, (const u64*)d_winmask_, cnt, d_wcnt_);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(orig_scan, dim3(1), dim3(SCAN_BS), 0, stream_, (const u32*)d_wcnt_, d_woff_, (u32)nblk, (unsigned long long*)d_ctr_);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(e5, stream_));
+    MatArgs m;
+    m.states = store_.states(); m.meta = store_.meta(); m.chunk_begin = cb - store_.base(); m.chunk_count = cnt; m.gid0 = cb;
+    m.winmask = d_winmask_; m.woff = d_woff_; m.ww = WW; m.dst_base = s.level_end() - store_.base(); m.cap = store_.cap();
+    m.rt = m_.rt; m.ctr = (unsigned long long*)d_ctr_;
+    hipLaunchKernelGGL((orig_materialize<S>), dim3(nblk), dim3(BS), 0, stream_, m);
+    return 0;
+  }
+
+  // The level's one host wait: the counters (left in h_ctr_), then the event times, the progress
+  // line, and the per-kernel accounting; s.nnew and s.level_ms are the level's.
+  int read_level(Search& s, RunResult& r, std::string& err) {
+    u64* const c = h_ctr_;   // pinned: the readback is one direct copy
+    HIPCHK(hipMemcpyAsync(c, d_ctr_, K_NCTR * 8, hipMemcpyDeviceToHost, stream_));
+    HIPCHK(hipEventRecord(ctr_ev_, stream_));
+    hipLaunchKernelGGL(orig_reset_ctr, dim3(1), dim3(64), 0, stream_, (unsigned long long*)d_ctr_);
+    HIPCHK(hipGetLastError());
+    ctr_clean_ = true;
+    // the host waits for the copy alone (the level's kernel events were all recorded before it):
+    // the reset behind it runs while the host looks at the counters
+    HIPCHK(hipEventSynchronize(ctr_ev_));
+    const bool fifo = s.fifo, last = s.last;
+    const u64 level_end = s.level_end(), S_B = NWP * 4;
+    double level_ms = 0;
+    for (int q = 0; q < s.nch; ++q) {
+      // event pairs per kernel (queue_level); dedup starts at e2 on a pipelined level, where e1 is
+      // the generate stream's.  On a pipelined level the pairs time kernels that share the device:
+      // their sum exceeds the time the device was busy.
+      const std::pair<int, int> pr[4] = {{0, 1}, {s.ovl ? 2 : 1, 3}, {3, fifo ? 5 : 3}, {fifo ? 5 : 3, 7}};
+      for (int k = 0; k < 4; ++k) {
+        float ms = 0;
+        if (pr[k].first != pr[k].second) (void)hipEventElapsedTime(&ms, pool_ev(8 * q + pr[k].first), pool_ev(8 * q + pr[k].second));
+        r.kernels[k].ms += ms; level_ms += ms;
+      }
+    }
+    const u64 nnew = c[K_LEVEL_NEW] + c[K_CHUNK_NEW];   // earlier chunks (orig_advance) + the last one
+    const u64 next_write = level_end + nnew;
+    if (progress_)   // TLC's progress line, per BFS level (RAFTMC_PROGRESS=1), on stderr
+      std::fprintf(stderr, "Progress(%lld) at %.3f s: %lld states generated, %llu distinct states found, %llu states left on queue "
+                           "(level kernels %.1f ms, %d chunk(s), store %llu/%llu, %llu on the host%s)\n",
+                   (long long)r.depth + 1,
+                   std::chrono::duration<double>(std::chrono::steady_clock::now() - s.t0).count(),
+                   (long long)(r.generated + (int64_t)[&] { u64 g = 0; for (int k = 0; k < OA_NACT; ++k) g += c[K_ACT + k]; return g; }()),
+                   (unsigned long long)(level_end + nnew), (unsigned long long)nnew, level_ms, s.nch,
+                   (unsigned long long)((last ? level_end : next_write) - store_.base()), (unsigned long long)store_.cap(), (unsigned long long)store_.base(),
+                   last ? "; the last level counted, not stored" : "");
+    if (progress_ && (c[K_EVENT] != ~0ull || c[K_ERR]))
+      std::fprintf(stderr, "level %lld: event word 0x%llx, error flags 0x%llx\n", (long long)r.depth + 1,
+                   (unsigned long long)c[K_EVENT], (unsigned long long)c[K_ERR]);
+    if (prof_) {
+      for (int q = 0; q < 4; ++q) prof_acc_[q] += c[K_PROF + q];
+      prof_acc_[4] = std::max<u64>(prof_acc_[4], c[K_PROF + 5]);
+    }
+    const u64 G_in = c[K_GEN_IN];
+    // per-kernel algorithmic bytes: generate writes 10-B records; dedup reads them and probes
+    // (8 B per in-model successor) and writes 16 B per new state; mark reads the
+    // inserted positions + keys and sets winner bits; materialize re-reads the parent and writes
+    // state + parent pointer
+    r.kernels[0].algo_bytes += (double)G_in * 10;
+    r.kernels[1].algo_bytes += (double)G_in * (10 + 8) + (double)nnew * (16 + 8);
+    r.kernels[2].algo_bytes += (double)nnew * (8 + 16 + 8);
+    r.kernels[3].algo_bytes += (double)s.level_count * WW * 8 + (double)nnew * (S_B + S_B + 8);
+    r.seconds_kernels += level_ms / 1000.0;
+    r.n_launches += 1;
+    s.nnew = nnew; s.level_ms = level_ms;
+    return 0;
+  }
+
+  // TLC -workers N found an event: TLC's counterexample and stop point are the single-worker
+  // search's, so the model is searched again in FIFO order (it stops at this level)
+  int research_fifo(const RunOpts& o, u64 evw, RunResult& r, std::string& err) {
+    RunOpts o1 = o;
+    o1.workers = 1;
+    o1.recover_path.clear();        // a checkpoint of this search is in its order, not TLC's: start over
+    o1.checkpoint_path.clear();
+    const int64_t ev_depth = r.depth + 1;
+    const int rc = run(o1, r, err);
+    if (rc == 0 && r.verdict == MC_VERDICT_CAPACITY_OVERFLOW) {
+      // the FIFO re-search stores every level (count_final_level included): when it does not
+      // fit, the event the -workers N pass found is still reported, not lost
+      static const char* const kind[4] = {"an evaluation error", "a deadlock", "an invariant evaluation error", "an invariant violation"};
+      r.error = std::string("the -workers N search found ") + kind[evw & 3] + " at depth " + std::to_string(ev_depth) +
+                "; TLC's single-worker re-search of it (for TLC's counterexample and stop point) ran out of capacity: " + r.error;
+    }
+    return rc;
+  }
+
+  // the text of a capacity verdict: c = the level's counters, whose K_ERR is not 0
+  std::string capacity_error(const u64* c, u64 level_end, u64 nnew, int64_t depth) const {
+    const u64 e = c[K_ERR];
+    std::ostringstream os;
+    os << "error flags 0x" << std::hex << e << std::dec << " while expanding state " << (c[K_ERRGID] ? (int64_t)(c[K_ERRGID] - 1) : -1) << ":";
+    if (e & OE_CAP_ELECTIONS) os << " elections set exceeds the compiled capacity;";
+    if (e & OE_CAP_COUNT) os << " message count / bag capacity exceeded;";
+    if (e & OE_CAP_STORE)
+      os << " state store full (raise state_store_bytes): " << store_.cap() << " state slots, " << store_.base()
+         << " states on the host, level ends at " << level_end << ", " << nnew << " new;";
+    if (e & OE_TABLE_FULL) os << " fingerprint table full (raise fp_table_bytes);";
+    // the summary counts the completed levels (their sizes sum to it, and the depth is theirs);
+    // whatever part of the interrupted level reached the store is not a level of the search
+    os << " the summary counts the " << level_end << " states of the " << depth << " completed levels;";
+    return os.str();
   }
 
   // TLC's stop point at the level's first event (key order = TLC's single-worker FIFO order):
@@ -2109,10 +2299,8 @@ class OrigGpu : public Backend {
       build_trace(pg, nullptr, s, r, err);
       return 0;
     }
-    u64 al[S::AW]; S::all_logs_next(s, al);
-    W t; u32 e2 = 0;
-    const int act = S::apply(s, (int)k, t, e2);
-    for (int q = 0; q < S::AW; ++q) t.allLogs[q] = al[q];
+    W t;
+    const int act = successor(s, (int)k, t);
     r.verdict = MC_VERDICT_INVARIANT_VIOLATION;
     r.violated = first_violated(S::violated(t, m_.rt.invariants));
     r.depth += 1;
@@ -2174,13 +2362,8 @@ class OrigGpu : public Backend {
     HIPCHK(hipMemsetAsync(d_ctr_, 0, K_NCTR * 8, stream_));
     HIPCHK(hipMemsetAsync(d_ctr_ + K_EVENT, 0xFF, 8, stream_));
     HIPCHK(hipStreamSynchronize(stream_));
-    sres_ = RunResult();
-    sres_.seed = o.seed ? o.seed : 0x5EED5EED2024ull;
-    sres_.state_bytes = NWP * 4;
-    for (int k = 0; k < OA_NACT; ++k) sres_.action_names.push_back(kOrigActNames[k]);
-    sres_.act_generated.assign(OA_NACT, 0); sres_.act_distinct.assign(OA_NACT, 0);
-    sres_.kernels = {{"orig_generate", 0, 0, 0}, {"orig_route_blk", 0, 0, 0}, {"orig_dedup_sh", 0, 0, 0},
-                     {"orig_materialize_sh", 0, 0, 0}, {"orig_store", 0, 0, 0}};
+    sres_ = new_result(bfs_seed(o), {"orig_generate", "orig_route_blk", "orig_dedup_sh", "orig_materialize_sh", "orig_store"});
+    pending_.clear();
     st0_ = std::chrono::steady_clock::now();
     // Init: one state, stored and inserted by the owner of its fingerprint
     W s0; S::init(s0);
@@ -2212,32 +2395,19 @@ class OrigGpu : public Backend {
     if (chunk) *chunk = (int64_t)chunk_states_;
     return 0;
   }
-  float time_ms(int a, int b) { float ms = 0; (void)hipEventElapsedTime(&ms, ev_[a], ev_[b]); return ms; }
-
+  // ---- the step API: each step queues one stage, waits for it and counts as one launch of its
+  // kernel, however many segments the stage launched
   int shard_generate(int64_t begin, int64_t count, int64_t* counts, std::string& err) override {
     if (begin < 0 || count < 0 || (u64)count > chunk_states_ || (u64)(begin + count) > sh_level_count_) { err = "shard_generate: chunk outside the frontier"; return MC_E_INVALID; }
     sh_chunk_begin_ = sh_level_begin_ + (u64)begin; sh_chunk_count_ = (u64)count;
-    HIPCHK(hipMemsetAsync(d_rcnt_, 0, 8 * 8, stream_));
-    if (count > 0) {
-      const GenArgs g = gen_args(sh_chunk_begin_, (u64)count, sh_chunk_begin_, sres_.seed, sopts_);
-      const RouteArgs ra = route_args((u32)world_);
-      const unsigned nblk = (unsigned)((count + BS - 1) / BS);
-      HIPCHK(hipEventRecord(ev_[5], stream_));
-      HIPCHK(hipMemsetAsync(d_ctr_ + K_LEAD, 0, 8, stream_));
-      launch_generate(g, nblk, stream_);
-      HIPCHK(hipGetLastError());
-      HIPCHK(hipEventRecord(ev_[6], stream_));
-      hipLaunchKernelGGL(orig_route_blk, dim3(nblk), dim3(BS), 0, stream_, ra);
-      HIPCHK(hipGetLastError());
-      HIPCHK(hipEventRecord(ev_[2], stream_));
-    }
+    if (int rc = stage_generate_route(err)) return rc;
     u64 c[8] = {0};
     HIPCHK(hipMemcpyAsync(c, d_rcnt_, 8 * 8, hipMemcpyDeviceToHost, stream_));
     HIPCHK(hipStreamSynchronize(stream_));
+    harvest();
     if (count > 0) {
       u64 valid = 0; for (int r = 0; r < world_; ++r) valid += c[r];
-      auto& ke = sres_.kernels[0]; ke.ms += time_ms(5, 6); ke.launches++; ke.algo_bytes += (double)count * NWP * 4;
-      auto& kr = sres_.kernels[1]; kr.ms += time_ms(6, 2); kr.launches++; kr.algo_bytes += (double)valid * 16;
+      sres_.kernels[1].algo_bytes += (double)valid * 16;
     }
     for (int r = 0; r < world_; ++r) { counts[r] = (int64_t)c[r]; fill_counts_route_[r] = c[r]; }
     return 0;
@@ -2260,71 +2430,41 @@ class OrigGpu : public Backend {
   }
 
   int shard_dedup(const void* recv, const int64_t* counts, int64_t* reply_counts, std::string& err) override {
-    u64 off = 0;
-    HIPCHK(hipMemsetAsync(d_rcnt_ + 8, 0, 8 * 8, stream_));
-    HIPCHK(hipEventRecord(ev_[0], stream_));
+    Seg seg[8];
     u64 total = 0;
-    for (int r = 0; r < world_; ++r) {
-      seg_off_[r] = off;
-      const u64 n = (u64)counts[r];
-      if (off + n > chunk_states_ * S::NI) { err = "shard_dedup: received more records than one chunk holds"; return MC_E_INVALID; }
-      if (n) {
-        DedupShArgs d;
-        d.recv = (const u64*)recv + 2 * off; d.n = n; d.table = d_table_; d.table_mask = sh_table_mask();
-        d.reply = d_newrec_ + off; d.counter = (unsigned long long*)(d_rcnt_ + 8 + r); d.ctr = (unsigned long long*)d_ctr_;
-        hipLaunchKernelGGL(orig_dedup_sh, dim3((unsigned)((n + BS * DEDUP_PER - 1) / (BS * DEDUP_PER))), dim3(BS), 0, stream_, d);
-        HIPCHK(hipGetLastError());
-      }
-      off += n; total += n;
-    }
-    HIPCHK(hipEventRecord(ev_[1], stream_));
+    for (int r = 0; r < world_; ++r) { seg[r] = {(const u64*)recv + 2 * total, (u64)counts[r]}; total += (u64)counts[r]; }
+    if (total > chunk_states_ * S::NI) { err = "shard_dedup: received more records than one chunk holds"; return MC_E_INVALID; }
+    auto& kd = sres_.kernels[2];
+    const int64_t steps = kd.launches + 1;
+    if (int rc = stage_dedup(seg, err)) return rc;
     u64 c[8] = {0};
     HIPCHK(hipMemcpyAsync(c, d_rcnt_ + 8, 8 * 8, hipMemcpyDeviceToHost, stream_));
     HIPCHK(hipStreamSynchronize(stream_));
+    harvest();
     u64 nnew = 0;
     for (int r = 0; r < world_; ++r) { reply_counts[r] = (int64_t)c[r]; fill_counts_reply_[r] = c[r]; nnew += c[r]; }
-    auto& kd = sres_.kernels[2]; kd.ms += time_ms(0, 1); kd.launches++; kd.algo_bytes += (double)total * 24 + (double)nnew * 16;
+    kd.launches = steps; kd.algo_bytes += (double)total * 24 + (double)nnew * 16;
     return 0;
   }
 
   int shard_materialize(const void* acks, const int64_t* counts, std::string& err) override {
+    Seg ack[8];
     u64 total = 0;
-    for (int r = 0; r < world_; ++r) { seg_off_ack_[r] = total; total += (u64)counts[r]; fill_counts_states_[r] = (u64)counts[r]; }
-    if (total > stout_cap_) {
-      if (d_stout_) (void)hipFree(d_stout_);
-      stout_cap_ = std::max<u64>(total, 1 << 16);
-      HIPCHK(hipMalloc(&d_stout_, stout_cap_ * (NWP + 4) * 4));
-    }
-    HIPCHK(hipEventRecord(ev_[0], stream_));
-    for (int r = 0; r < world_; ++r) {
-      const u64 n = (u64)counts[r];
-      if (!n) continue;
-      MatShArgs m;
-      m.states = store_.states(); m.acks = (const u64*)acks + seg_off_ack_[r]; m.n = n; m.chunk_begin = sh_chunk_begin_;
-      m.chunk_count = sh_chunk_count_; m.out = d_stout_ + seg_off_ack_[r] * (NWP + 4); m.rank_bits = (u64)rank_ << 37;
-      m.seed = sres_.seed; m.rt = m_.rt; m.ctr = (unsigned long long*)d_ctr_;
-      m.st_states = nullptr; m.st_meta = nullptr; m.st_dst = 0; m.st_cap = 0; m.store = 1;
-      hipLaunchKernelGGL((orig_materialize_sh<S>), dim3((unsigned)((n + BS - 1) / BS)), dim3(BS), 0, stream_, m);
-      HIPCHK(hipGetLastError());
-    }
-    HIPCHK(hipEventRecord(ev_[1], stream_));
+    for (int r = 0; r < world_; ++r) { ack[r] = {(const u64*)acks + total, (u64)counts[r]}; total += (u64)counts[r]; fill_counts_states_[r] = (u64)counts[r]; }
+    auto& km = sres_.kernels[3];
+    const int64_t steps = km.launches + 1;
+    if (int rc = stage_rederive(ack, false, -1, 0, err)) return rc;
     HIPCHK(hipStreamSynchronize(stream_));
-    auto& km = sres_.kernels[3]; km.ms += time_ms(0, 1); km.launches++; km.algo_bytes += (double)total * (8 + NWP * 4 + (NWP + 4) * 4);
+    harvest();
+    km.launches = steps;
     return 0;
   }
 
   int shard_store(const void* states, int64_t n, std::string& err) override {
     if (n <= 0) return 0;
-    StoreArgs a;
-    a.in = (const u32*)states; a.n = (u64)n; a.dst = sh_next_write_; a.cap = store_.cap(); a.states = store_.states(); a.meta = store_.meta();
-    a.ctr = (unsigned long long*)d_ctr_;
-    HIPCHK(hipEventRecord(ev_[0], stream_));
-    hipLaunchKernelGGL((orig_store<NWP>), dim3((unsigned)((n + BS - 1) / BS)), dim3(BS), 0, stream_, a);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ev_[1], stream_));
+    if (int rc = stage_store((const u32*)states, (u64)n, err)) return rc;
     HIPCHK(hipStreamSynchronize(stream_));
-    auto& ks = sres_.kernels[4]; ks.ms += time_ms(0, 1); ks.launches++; ks.algo_bytes += (double)n * ((NWP + 4) * 4 + NWP * 4 + 8);
-    sh_next_write_ += (u64)n; sh_new_ += (u64)n;
+    harvest();
     return 0;
   }
 
@@ -2385,10 +2525,7 @@ class OrigGpu : public Backend {
         u32 w[NWP];
         if (hipMemcpy(w, store_.states() + par * NWP, NWP * 4, hipMemcpyDeviceToHost) == hipSuccess) {
           W s, t; S::unpack(w, s);
-          u64 al[S::AW]; S::all_logs_next(s, al);
-          u32 e2 = 0;
-          const int act = S::apply(s, k, t, e2);
-          for (int q = 0; q < S::AW; ++q) t.allLogs[q] = al[q];
+          const int act = successor(s, k, t);
           sviol_bad_ = S::violated(t, m_.rt.invariants);
           sviol_parent_ = ((u64)rank_ << 37) | par; sviol_act_ = act >= 0 ? kOrigActNames[act] : "?";
           sviol_text_ = state_text(t, true);
@@ -2429,8 +2566,8 @@ class OrigGpu : public Backend {
   int shard_run_native(ShardTransport& T, std::string& err) override {
     const int W = world_, me = rank_;
     const u64 SBW = (u64)(NWP + 4) * 4;          // STATES record bytes
-    if (!d_nat_) HIPCHK(hipMalloc(&d_nat_, (32 + 2 * MC_SHARD_NSTAT) * 8));
-    if (!h_nat_) HIPCHK(hipHostMalloc(&h_nat_, (32 + 2 * MC_SHARD_NSTAT) * 8));
+    if (!d_nat_) HIPCHK(res_.device(&d_nat_, (32 + 2 * MC_SHARD_NSTAT) * 8));
+    if (!h_nat_) HIPCHK(res_.pinned(&h_nat_, (32 + 2 * MC_SHARD_NSTAT) * 8));
     u64* d_xs = d_nat_;        // [0,8) counts I send  (copied from d_rcnt_)
     u64* d_xr = d_nat_ + 8;    // [8,16) counts I receive
     int64_t* d_sum = (int64_t*)(d_nat_ + 32);
@@ -2438,14 +2575,6 @@ class OrigGpu : public Backend {
     u64* h_xs = h_nat_; u64* h_xr = h_nat_ + 8;
     int64_t* h_sum = (int64_t*)(h_nat_ + 32);
     int64_t* h_max = h_sum + MC_SHARD_NSTAT;
-    // grow-only device buffer
-    auto grow = [&](void*& p, u64& cap, u64 need) -> int {
-      if (need <= cap) return 0;
-      if (p) { HIPCHK(hipStreamSynchronize(stream_)); HIPCHK(hipFree(p)); p = nullptr; }
-      cap = std::max<u64>(need + need / 4, 1 << 20);
-      HIPCHK(hipMalloc(&p, cap));
-      return 0;
-    };
     // counts exchange: send[r] from d_send (device), received into d_xr; both land on the host
     auto xcounts = [&](const u64* d_send) -> int {
       HIPCHK(hipMemcpyAsync(d_xs, d_send, 8 * (u64)W, hipMemcpyDeviceToDevice, stream_));
@@ -2469,32 +2598,6 @@ class OrigGpu : public Backend {
       if (W > 1 && T.exchange(me, W, src, sbytes, dsts, rbytes, stream_, err)) return MC_E_NO_DEVICE;
       return 0;
     };
-    // HIP-event timing, read back at the level's synchronisation points
-    std::vector<std::pair<int, int>> pending;   // (kernel index, event pair index)
-    auto ev_pair = [&](int k) -> int {
-      const int i = (int)pending.size();
-      while ((int)nat_ev_.size() < 2 * (i + 1)) { hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) return -1; nat_ev_.push_back(e); }
-      pending.push_back({k, i});
-      return i;
-    };
-    auto harvest = [&]() {
-      for (auto& pr : pending) {
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, nat_ev_[2 * pr.second], nat_ev_[2 * pr.second + 1]);
-        sres_.kernels[pr.first].ms += ms;
-      }
-      pending.clear();
-    };
-#define NAT_TIMED(k, launch)                                                   \
-  do {                                                                         \
-    const int ep_ = ev_pair(k);                                                \
-    if (ep_ < 0) { err = "hipEventCreate failed"; return MC_E_NO_DEVICE; }     \
-    HIPCHK(hipEventRecord(nat_ev_[2 * ep_], stream_));                         \
-    launch;                                                                    \
-    HIPCHK(hipGetLastError());                                                 \
-    HIPCHK(hipEventRecord(nat_ev_[2 * ep_ + 1], stream_));                     \
-    sres_.kernels[k].launches++;                                               \
-  } while (0)
     auto allreduce_level = [&](int64_t* g, int64_t next_chunks, int64_t& chunks_out) -> int {
       // g: local stats in, global stats out; MAX slots: [3,6) flags, [6] chunk rounds of the next
       // level, [8, 8+32) one slot per bit of the error word (max per bit = bitwise OR over ranks:
@@ -2548,36 +2651,19 @@ class OrigGpu : public Backend {
           // probes the owner's, orig_materialize_plain stores the new states behind the level; the
           // counts stay on the device (orig_advance), the host waits once per level
           if (count == 0) continue;
-          const GenArgs g = gen_args(sh_chunk_begin_, count, sh_chunk_begin_, sres_.seed, sopts_);
           const unsigned nblk = (unsigned)((count + BS - 1) / BS);
-          HIPCHK(hipMemsetAsync(d_ctr_ + K_LEAD, 0, 8, stream_));
-          NAT_TIMED(0, launch_generate(g, nblk, stream_));
-          sres_.kernels[0].algo_bytes += (double)count * NWP * 4;
-          DedupArgs d;
-          d.rfp = d_rfp_; d.rkey = d_rkey_; d.rcnt = d_rcnt_blk_; d.region = (u64)BS * S::NI; d.gid0 = sh_chunk_begin_;
-          d.urec = (ulonglong2*)d_urec_; d.ucnt = d_ucnt_;
-          d.table = d_table_; d.table_mask = sh_table_mask(); d.newpos = d_newrec_; d.ctr = (unsigned long long*)d_ctr_;
-          d.prof = 0;
-          NAT_TIMED(2, hipLaunchKernelGGL((orig_dedup_plain<WW, false>), dim3(nblk), dim3(BS), 0, stream_, d));
-          MatPlainArgs m;
-          m.states = store_.states(); m.meta = store_.meta(); m.newrec = d_newrec_; m.base = 0; m.dst_base = sh_next_write_;
-          m.cap = store_.cap(); m.rt = m_.rt; m.ctr = (unsigned long long*)d_ctr_; m.store = last ? 0u : 1u;
-          NAT_TIMED(3, hipLaunchKernelGGL((orig_materialize_plain<S>), dim3((unsigned)std::min<u64>(4096, (count * 2 + BS - 1) / BS)),
-                                          dim3(BS), 0, stream_, m));
+          const GenArgs g = sh_gen_args();
+          if (int rc = stage_generate(g, nblk, err)) return rc;
+          DedupArgs d = dedup_args(g, sh_chunk_begin_, d_table_, sh_table_mask());
+          d.prof = 0;   // (RAFTMC_PROF reads the counters of mc_run's levels only)
+          if (int rc = timed(2, [&] { launch_dedup_plain(d, nblk, 0, false); }, err)) return rc;
+          const MatPlainArgs m = mat_plain_args(0, sh_next_write_, !last);
+          if (int rc = timed(3, [&] { launch_materialize_plain(m, count); }, err)) return rc;
           hipLaunchKernelGGL(orig_advance, dim3(1), dim3(64), 0, stream_, (unsigned long long*)d_ctr_, 1);
           HIPCHK(hipGetLastError());
           continue;
         }
-        HIPCHK(hipMemsetAsync(d_rcnt_, 0, 16 * 8, stream_));
-        if (count > 0) {
-          const GenArgs g = gen_args(sh_chunk_begin_, count, sh_chunk_begin_, sres_.seed, sopts_);
-          const unsigned nblk = (unsigned)((count + BS - 1) / BS);
-          HIPCHK(hipMemsetAsync(d_ctr_ + K_LEAD, 0, 8, stream_));
-          NAT_TIMED(0, launch_generate(g, nblk, stream_));
-          sres_.kernels[0].algo_bytes += (double)count * NWP * 4;
-          const RouteArgs ra = route_args((u32)W);
-          NAT_TIMED(1, hipLaunchKernelGGL(orig_route_blk, dim3(nblk), dim3(BS), 0, stream_, ra));
-        }
+        if (int rc = stage_generate_route(err)) return rc;
         // ---- ROUTE: (fp, slot) records to the fingerprints' owners
         if (int rc = xcounts(d_rcnt_)) return rc;
         u64 scnt[8], rcnt[8], sb[8], rb[8], rtot = 0;
@@ -2589,24 +2675,16 @@ class OrigGpu : public Backend {
           sres_.kernels[1].algo_bytes += (double)scnt[r] * 16;
         }
         if (rtot > route_cap) { err = "shard: received more ROUTE records than one chunk holds"; return MC_E_STATE; }
-        if (int rc = grow(nat_recv_, nat_recv_cap_, rtot * 16)) return rc;
+        if (int rc = grow(nat_recv_, nat_recv_cap_, rtot * 16, err)) return rc;
         if (int rc = xpay(src, sb, (char*)nat_recv_, rb)) return rc;
-        // ---- owner-side dedup, one launch per source rank
-        {
-          u64 off = 0;
-          for (int r = 0; r < W; ++r) {
-            seg_off_[r] = off;
-            const u64 n = rcnt[r];
-            if (n) {
-              DedupShArgs d;
-              d.recv = r == me ? d_route_ + (u64)me * route_cap * 2 : (const u64*)nat_recv_ + 2 * off;
-              d.n = n; d.table = d_table_; d.table_mask = sh_table_mask();
-              d.reply = d_newrec_ + off; d.counter = (unsigned long long*)(d_rcnt_ + 8 + r); d.ctr = (unsigned long long*)d_ctr_;
-              NAT_TIMED(2, hipLaunchKernelGGL(orig_dedup_sh, dim3((unsigned)((n + BS * DEDUP_PER - 1) / (BS * DEDUP_PER))), dim3(BS), 0, stream_, d));
-            }
-            off += n;
-          }
+        // ---- owner-side dedup, one launch per source rank (the self segment where route left it)
+        Seg seg[8];
+        u64 off = 0;
+        for (int r = 0; r < W; ++r) {
+          seg[r] = {r == me ? d_route_ + (u64)me * route_cap * 2 : (const u64*)nat_recv_ + 2 * off, rcnt[r]};
+          off += rcnt[r];
         }
+        if (int rc = stage_dedup(seg, err)) return rc;
         // ---- REPLY: the new ones' slots back to the generating ranks
         if (int rc = xcounts(d_rcnt_ + 8)) return rc;
         u64 rep[8], ack[8], atot = 0, ntot = 0;
@@ -2616,58 +2694,33 @@ class OrigGpu : public Backend {
           src[r] = (const char*)(d_newrec_ + seg_off_[r]);
         }
         sres_.kernels[2].algo_bytes += (double)rtot * 24 + (double)ntot * 16;
-        if (int rc = grow(nat_acks_, nat_acks_cap_, atot * 8)) return rc;
+        if (int rc = grow(nat_acks_, nat_acks_cap_, atot * 8, err)) return rc;
         if (int rc = xpay(src, sb, (char*)nat_acks_, rb)) return rc;
-        // ---- generator re-derives the acknowledged states
-        {
-          u64 off = 0;
-          for (int r = 0; r < W; ++r) { seg_off_ack_[r] = off; off += ack[r]; }
-          if (!last) {
-            void* so = d_stout_;
-            u64 socap = stout_cap_ * SBW;
-            if (int rc = grow(so, socap, atot * SBW)) return rc;
-            d_stout_ = (u32*)so; stout_cap_ = socap / SBW;
-          }
-          for (int r = 0; r < W; ++r) {
-            if (!ack[r]) continue;
-            MatShArgs m;
-            m.states = store_.states(); m.acks = r == me ? d_newrec_ + seg_off_[me] : (const u64*)nat_acks_ + seg_off_ack_[r];
-            m.n = ack[r]; m.chunk_begin = sh_chunk_begin_;
-            m.chunk_count = sh_chunk_count_; m.out = last ? nullptr : d_stout_ + seg_off_ack_[r] * (NWP + 4); m.rank_bits = (u64)me << 37;
-            m.seed = sres_.seed; m.rt = m_.rt; m.ctr = (unsigned long long*)d_ctr_;
-            m.st_states = nullptr; m.st_meta = nullptr; m.st_dst = 0; m.st_cap = 0; m.store = last ? 0u : 1u;
-            if (r == me && !last) {   // my own new states: into my store after the ones of lower ranks
-              u64 before = 0; for (int q = 0; q < me; ++q) before += rep[q];
-              m.st_states = store_.states(); m.st_meta = store_.meta(); m.st_dst = sh_next_write_ + before; m.st_cap = store_.cap();
-            }
-            NAT_TIMED(3, hipLaunchKernelGGL((orig_materialize_sh<S>), dim3((unsigned)((ack[r] + BS - 1) / BS)), dim3(BS), 0, stream_, m));
-          }
-          sres_.kernels[3].algo_bytes += (double)atot * (8 + NWP * 4 + (last ? 0 : SBW));
+        // ---- generator re-derives the acknowledged states; my own new ones go into my store
+        // after the ones of lower ranks
+        u64 before = 0;
+        for (int q = 0; q < me; ++q) before += rep[q];
+        off = 0;
+        for (int r = 0; r < W; ++r) {
+          seg[r] = {r == me ? d_newrec_ + seg_off_[me] : (const u64*)nat_acks_ + off, ack[r]};
+          off += ack[r];
         }
+        if (int rc = stage_rederive(seg, last, me, sh_next_write_ + before, err)) return rc;
         if (last) {   // the owners count their new states of the final level; nothing is shipped
           for (int r = 0; r < W; ++r) sh_new_ += rep[r];
           continue;
         }
         // ---- STATES: packed states + parent pointers to their owners (sizes known: no sync)
         for (int r = 0; r < W; ++r) { sb[r] = ack[r] * SBW; rb[r] = rep[r] * SBW; src[r] = (const char*)(d_stout_ + seg_off_ack_[r] * (NWP + 4)); }
-        if (int rc = grow(nat_stin_, nat_stin_cap_, ntot * SBW)) return rc;
+        if (int rc = grow(nat_stin_, nat_stin_cap_, ntot * SBW, err)) return rc;
         if (int rc = xpay(src, sb, (char*)nat_stin_, rb)) return rc;
-        {   // the owner stores the states in source-rank order (its own ones were materialized in place)
-          u64 in_off = 0;
-          for (int r = 0; r < W; ++r) {
-            const u64 n = rep[r];
-            if (n && r == me) { sh_next_write_ += n; sh_new_ += n; }
-            else if (n) {
-              StoreArgs a;
-              a.in = (const u32*)((const char*)nat_stin_ + in_off * SBW);
-              a.n = n; a.dst = sh_next_write_; a.cap = store_.cap(); a.states = store_.states(); a.meta = store_.meta();
-              a.ctr = (unsigned long long*)d_ctr_;
-              NAT_TIMED(4, hipLaunchKernelGGL((orig_store<NWP>), dim3((unsigned)((n + BS - 1) / BS)), dim3(BS), 0, stream_, a));
-              sres_.kernels[4].algo_bytes += (double)n * (SBW + NWP * 4 + 8);
-              sh_next_write_ += n; sh_new_ += n;
-            }
-            in_off += n;
-          }
+        // the owner stores the states in source-rank order (its own ones were materialized in place)
+        off = 0;
+        for (int r = 0; r < W; ++r) {
+          if (rep[r] && r == me) { sh_next_write_ += rep[r]; sh_new_ += rep[r]; }
+          else if (rep[r])
+            if (int rc = stage_store((const u32*)((const char*)nat_stin_ + off * SBW), rep[r], err)) return rc;
+          off += rep[r];
         }
       }
       HIPCHK(hipStreamSynchronize(stream_));
@@ -2692,7 +2745,6 @@ class OrigGpu : public Backend {
       if (done) break;
       nchunks = next_chunks;
     }
-#undef NAT_TIMED
     return 0;
   }
 
@@ -2704,10 +2756,10 @@ class OrigGpu : public Backend {
   bool ctr_clean_ = false;   // d_ctr_ already reset for the next level (queued after the readback)
   u64* d_rfp_ = nullptr; unsigned short* d_rkey_ = nullptr; u32* d_rcnt_blk_ = nullptr; u64* d_newrec_ = nullptr;
   u64* d_winmask_ = nullptr; u32* d_wcnt_ = nullptr; u64* d_woff_ = nullptr; u64* d_urec_ = nullptr; u32* d_ucnt_ = nullptr;
-  u64* d_route_ = nullptr; u64* d_rcnt_ = nullptr; u32* d_stout_ = nullptr; u64 stout_cap_ = 0;
+  u64* d_route_ = nullptr; u64* d_rcnt_ = nullptr;
+  u32* d_stout_ = nullptr; u64 stout_cap_ = 0;   // re-derived STATES records (stage_rederive), its bytes
   u32* d_lead_ = nullptr;      // [chunk] the chunk's leader-work parents (orig_generate -> orig_generate_lead)
   hipStream_t stream_ = nullptr;
-  hipEvent_t ev_[9] = {};
   hipEvent_t ctr_ev_ = nullptr;          // recorded behind the level's counter readback
   // the starter seen-set (ensure_starter) and the stream / event of the full table's clear
   u64* d_starter_ = nullptr; u64 starter_cap_ = 0;
@@ -2737,42 +2789,33 @@ class OrigGpu : public Backend {
   u64* d_nat_ = nullptr; u64* h_nat_ = nullptr;
   void* nat_recv_ = nullptr; void* nat_acks_ = nullptr; void* nat_stin_ = nullptr;
   u64 nat_recv_cap_ = 0, nat_acks_cap_ = 0, nat_stin_cap_ = 0;
-  std::vector<hipEvent_t> nat_ev_;
-  std::vector<hipEvent_t> lvl_ev_;
+  std::vector<int> pending_;   // sharded stages: the kernel of each event pair not yet read back (timed / harvest)
   StateStore store_;   // the stored states and parent pointers: device part + host spill
+  // owns every device and pinned allocation, event and stream named above (and the pool of timing
+  // events): each is created through it, and release() frees them all
+  DevOwner<HipDevApi> res_;
 
   void release_device() override { release(); }
   void release() {
     // a run that returned early may have left the full table's clear in flight
-    if (clear_stream_) { (void)hipStreamSynchronize(clear_stream_); (void)hipStreamDestroy(clear_stream_); clear_stream_ = nullptr; }
+    if (clear_stream_) (void)hipStreamSynchronize(clear_stream_);
     if (stream_) (void)hipStreamSynchronize(stream_);
-    if (clear_ev_) { (void)hipEventDestroy(clear_ev_); clear_ev_ = nullptr; }
-    if (gen_ev_) { (void)hipEventDestroy(gen_ev_); gen_ev_ = nullptr; }
-    if (ctr_ev_) { (void)hipEventDestroy(ctr_ev_); ctr_ev_ = nullptr; }
-    if (d_starter_) { (void)hipFree(d_starter_); d_starter_ = nullptr; starter_cap_ = 0; }
-    run_table_ = nullptr; run_mask_ = 0;
-    for (void* p : {(void*)d_table_, (void*)d_ctr_, (void*)d_stop_, (void*)d_rfp_, (void*)d_rkey_,
-                    (void*)d_rcnt_blk_, (void*)d_newrec_, (void*)d_winmask_, (void*)d_wcnt_, (void*)d_woff_, (void*)d_urec_, (void*)d_ucnt_,
-                    (void*)d_route_, (void*)d_rcnt_, (void*)d_stout_, (void*)d_lead_})
-      if (p) (void)hipFree(p);
-    for (void* p : {(void*)d_nat_, nat_recv_, nat_acks_, nat_stin_})
-      if (p) (void)hipFree(p);
-    if (h_nat_) (void)hipHostFree(h_nat_);
-    d_nat_ = nullptr; h_nat_ = nullptr; nat_recv_ = nat_acks_ = nat_stin_ = nullptr;
-    nat_recv_cap_ = nat_acks_cap_ = nat_stin_cap_ = 0;
-    for (auto& e : nat_ev_) (void)hipEventDestroy(e);
-    nat_ev_.clear();
-    for (auto& e : lvl_ev_) (void)hipEventDestroy(e);
-    lvl_ev_.clear();
-    for (auto& e : ev_) { if (e) (void)hipEventDestroy(e); e = nullptr; }
-    if (stream_) (void)hipStreamDestroy(stream_);
-    if (h_ctr_) (void)hipHostFree(h_ctr_);
-    h_ctr_ = nullptr; ctr_clean_ = false;
+    res_.release();   // streams last
     store_.release();
-    d_table_ = nullptr; d_ctr_ = nullptr; d_stop_ = nullptr;
-    d_rfp_ = nullptr; d_rkey_ = nullptr; d_rcnt_blk_ = nullptr; d_newrec_ = nullptr; d_winmask_ = nullptr; d_wcnt_ = nullptr; d_woff_ = nullptr; d_urec_ = nullptr; d_ucnt_ = nullptr; d_route_ = nullptr; d_rcnt_ = nullptr; d_stout_ = nullptr; stout_cap_ = 0;
-    d_lead_ = nullptr;
-    stream_ = nullptr; alloc_world_ = 0;
+    starter_cap_ = 0; stout_cap_ = 0; nat_recv_cap_ = nat_acks_cap_ = nat_stin_cap_ = 0;
+    run_table_ = nullptr; run_mask_ = 0;
+    pending_.clear();
+    ctr_clean_ = false;
+    dev_ = -1; alloc_world_ = 0;   // nothing allocated: the next ensure_alloc starts over
+  }
+
+  // successor k of s as the search keeps it (allLogs advanced), and the action that made it (< 0: none)
+  static int successor(const W& s, int k, W& t) {
+    u64 al[S::AW]; S::all_logs_next(s, al);
+    u32 e2 = 0;
+    const int act = S::apply(s, k, t, e2);
+    for (int q = 0; q < S::AW; ++q) t.allLogs[q] = al[q];
+    return act;
   }
 
   std::string first_violated(u32 bad) const {
