@@ -209,17 +209,27 @@ int mc_action_location(const mc_ctx* ctx, const char* action, char** text, size_
  * report's estimate line. */
 int mc_collision_observed(mc_ctx* ctx, double* val);
 
-/* Checkpoint / recover (both spec families) — TLC's `-checkpoint <minutes>` and `-recover <dir>`
+/* Checkpoint / recover (the two hand-compiled families and the generated path) — TLC's
+ * `-checkpoint <minutes>` and `-recover <dir>`
  * (the states/ directory, reference .gitignore:3).  mc_set_checkpoint: every `every_levels`
  * completed BFS levels mc_run writes the search state (stored states, parent pointers, level
  * position, TLC's counters, the model's identity) to `path` (atomically: path.tmp, rename);
  * NULL or 0 disables.  mc_set_recover: the next mc_run resumes from `path` instead of Init
  * (the seen-set is rebuilt on the GPU from the stored states); generated/distinct/depth/per-action
  * counts continue exactly; kernel timings cover the resumed part.  A checkpoint of another
- * model (or of the other SYMMETRY mode, or — raft_original — a -workers N checkpoint for a -workers 1
- * search) is refused (MC_E_INVALID).  Completed levels that do not fit the device store are kept in
- * host memory on save and on recovery (host spill).  Single-GPU runs only: the mc_shard_* calls
- * return MC_E_UNSUPPORTED on a handle with a checkpoint or recover path set. */
+ * model or of another backend (or of the other SYMMETRY mode, or — raft_original and the generated
+ * path — a -workers N checkpoint for a -workers 1 search: its kept parents are not TLC's; a
+ * -workers 1 checkpoint does resume a -workers N search) is refused (MC_E_INVALID), a truncated or
+ * unreadable file MC_E_IO.  fp_table_bytes and state_store_bytes may be larger on recovery than when
+ * the file was written (the seen-set is rebuilt at this run's size): that is how a run that ended
+ * as CAPACITY_OVERFLOW goes on from its last checkpoint, which an overflow never overwrites.
+ * Hand-compiled families: completed levels that do not fit the device store are kept in host
+ * memory on save and on recovery (host spill).  The generated path has no host spill: a file that
+ * does not fit the configured store or table ends as CAPACITY_OVERFLOW ("state store full",
+ * "seen-set full"); it identifies the model by the generated code's key and its variable and
+ * action names, not by the module's path.  A -workers N search that finds an event searches the
+ * model again in FIFO order from Init, with neither path.  Single-GPU runs only: the mc_shard_*
+ * calls return MC_E_UNSUPPORTED on a handle with a checkpoint or recover path set. */
 int mc_set_checkpoint(mc_ctx* ctx, const char* path, int32_t every_levels);
 int mc_set_recover(mc_ctx* ctx, const char* path);
 

@@ -1,11 +1,12 @@
 // raftmc host: the framing of a checkpoint file (TLC -checkpoint / -recover),
-// shared by the spec families.  Host-only: no HIP header, so it compiles with a plain C++ compiler
-// (tests/native/ckpt_file_check.cpp).
+// shared by the spec families and the generated path.  Host-only: no HIP header, so it compiles with
+// a plain C++ compiler (tests/native/ckpt_file_check.cpp, tests/native/tlagen_ckpt_check.cpp).
 //
-// File: the family's 112-byte header (magic, the BFS position, TLC's counters), the model's
-// describe_json text (a checkpoint only resumes the same model), the per-action generated and
-// distinct counters, (states, generated) per level, then the stored states and parent pointers
-// [0, total) in global-id order (state_store.h).  The seen-set is rebuilt from the states on recovery.
+// File: the backend's header (magic, the BFS position, TLC's counters), the text that names the model
+// (a checkpoint only resumes the same model), the per-action generated and distinct counters,
+// (states, generated) per level, then the stored states [0, total) in global-id order: fixed-width
+// states and parent pointers (state_store.h), or the generated path's four arrays (GenHead).  The
+// seen-set is rebuilt from the states on recovery.
 #pragma once
 #include <stdint.h>
 
@@ -19,7 +20,7 @@
 
 namespace rmc::ckpt {
 
-// The two on-disk headers, field order as written since their magics were introduced (the shared
+// The on-disk headers, field order as written since their magics were introduced (the shared
 // code below reads magic, nwp, n_act, n_levels and desc_len by name and copies the rest as bytes).
 struct OrigHead {   // raft_original, "RAFTMCK2"
   char magic[8];
@@ -37,7 +38,19 @@ struct MembHead {   // tlc_membership, "RAFTMCM1"
   uint64_t sym_tlc;   // the SYMMETRY mode the fingerprints were taken in (MC_COMPAT_SYM_TLC)
   int64_t generated, distinct, depth, generated_in_model, n_act, n_levels, desc_len;
 };
+// The generated path (csrc/tlagen), "RAFTMCG1": states are variable-width runs of canonical words,
+// so nwp is 0 and the body is four arrays in global-id order, offs[total] (a state's first word),
+// parent[total], act[total], words[words].  The writer lays the words out in id order: offs[0] = 0,
+// offs ascends and state i ends where state i + 1 (or the array) begins.  fifo: as OrigHead's.
+struct GenHead {
+  char magic[8];
+  uint64_t nwp, total, level_begin, level_count, seed;
+  uint64_t words;     // canonical words stored
+  int64_t fifo;
+  int64_t generated, distinct, depth, generated_in_model, n_act, n_levels, desc_len;
+};
 static_assert(sizeof(OrigHead) == 112 && sizeof(MembHead) == 112, "the checkpoint headers are 112 bytes on disk");
+static_assert(sizeof(GenHead) == 120, "the generated path's checkpoint header is 120 bytes on disk");
 
 // a FILE* that is closed on every path (null when it could not be opened)
 using File = std::unique_ptr<FILE, int (*)(FILE*)>;
@@ -91,5 +104,57 @@ class Reader {
   std::string path_;
   File f_;
 };
+
+// The generated path's file behind Reader::head.  Every value a recovery later indexes with is
+// checked on the host before anything is indexed: by check_gen_head the header's counts against
+// each other, the levels and the file's length (so `total` and `words` are what the file holds);
+// by read_gen_body offs against the writer's layout (GenHead) and a parent before its child
+// (initial states, the first level, have none).  A file that fails is no checkpoint of this model.
+template <class Levels>
+int check_gen_head(Reader& in, const GenHead& h, const Levels& levels, std::string& err) {
+  uint64_t in_levels = 0;
+  for (const auto& lv : levels) {
+    if (lv.states <= 0 || (uint64_t)lv.states > h.total) return in.other_model(err);
+    in_levels += (uint64_t)lv.states;
+  }
+  if (h.total == 0 || h.total >= (1ull << 40) || h.words < h.total || h.words >= (1ull << 48) || in_levels != h.total ||
+      h.level_count != (uint64_t)levels.back().states || h.level_begin != h.total - h.level_count ||
+      h.depth != h.n_levels || h.distinct != (int64_t)h.total || (h.fifo != 0 && h.fifo != 1))
+    return in.other_model(err);
+  const long at = std::ftell(in.file());
+  if (at < 0 || std::fseek(in.file(), 0, SEEK_END) != 0) return in.truncated(err);
+  const long end = std::ftell(in.file());
+  if (end < at || std::fseek(in.file(), at, SEEK_SET) != 0) return in.truncated(err);
+  const uint64_t body = h.total * 20 + h.words * 4;
+  if ((uint64_t)(end - at) < body) return in.truncated(err);
+  if ((uint64_t)(end - at) > body) return in.other_model(err);
+  return 0;
+}
+// The four arrays (after check_gen_head), read in chunks of at most chunk_bytes and handed to
+// sink(kind, data, first, n, err) -> 0 or an error code: kind 0 offs, 1 parent, 2 act, 3 words;
+// data[0] is element `first` of its array.  n_init: the initial states (the first level).
+template <class Sink>
+int read_gen_body(Reader& in, const GenHead& h, uint64_t n_init, size_t chunk_bytes, Sink sink, std::string& err) {
+  const uint64_t most = h.total > (h.words + 1) / 2 ? h.total : (h.words + 1) / 2;   // the longest array, in 8-byte units
+  std::vector<uint64_t> buf(chunk_bytes / 8 == 0 ? 1 : chunk_bytes / 8 < most ? chunk_bytes / 8 : most);
+  uint64_t prev_off = 0;
+  for (int kind = 0; kind < 4; ++kind) {
+    const size_t esz = kind < 2 ? 8 : 4;
+    const uint64_t len = kind == 3 ? h.words : h.total, per = buf.size() * 8 / esz;
+    for (uint64_t first = 0; first < len; first += per) {
+      const uint64_t n = len - first < per ? len - first : per;
+      if (std::fread(buf.data(), esz, n, in.file()) != n) return in.truncated(err);
+      for (uint64_t k = 0; kind == 0 && k < n; ++k) {
+        const uint64_t o = buf[k];
+        if (first + k == 0 ? o != 0 : (o <= prev_off || o >= h.words)) return in.other_model(err);
+        prev_off = o;
+      }
+      for (uint64_t k = 0; kind == 1 && k < n; ++k)
+        if (first + k < n_init ? buf[k] != ~0ull : buf[k] >= first + k) return in.other_model(err);
+      if (int rc = sink(kind, (const void*)buf.data(), first, n, err)) return rc;
+    }
+  }
+  return 0;
+}
 
 }  // namespace rmc::ckpt

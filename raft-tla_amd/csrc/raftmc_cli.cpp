@@ -12,7 +12,10 @@
 // stored; mc_opts.count_final_level)
 // (-gpus N: the node's GPUs -device .. -device+N-1 share one search, owner-partitioned fingerprints,
 // one host thread per GPU over an in-process RCCL communicator; TLC's -workers keeps its meaning)
-// (-checkpoint counts BFS levels where TLC counts minutes; the file defaults to states/raftmc.ckpt)
+// (-checkpoint counts BFS levels where TLC counts minutes; the file defaults to states/raftmc.ckpt.
+// Both hand-compiled families and the generated path write and recover one; -recover takes a larger
+// -fptable / -store than the writer had, which is how a run that ended as "state store full" or
+// "seen-set full" goes on from its last checkpoint)
 // Prints TLC-style lines and exits with TLC-like codes (0 ok, 12 safety
 // violation, 11 deadlock, 75 error).
 #include <cstdio>

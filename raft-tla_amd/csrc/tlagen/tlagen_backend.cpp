@@ -22,6 +22,7 @@
 
 #include "../../../include/raftmc.h"
 #include "../backend.h"
+#include "../ckpt_file.h"
 #include "tla_gen.h"
 #include "tlv_text.h"
 
@@ -29,6 +30,10 @@ namespace rmc {
 
 int tlagen_sort_keys(const unsigned long long* keys_in, unsigned long long* keys_out, unsigned long long n, int bits,
                      void** tmp, size_t* tmp_bytes, hipStream_t s);   // tlagen_sort.hip
+int tlagen_state_sizes(const unsigned int* words, unsigned long long used, const unsigned long long* offs, unsigned long long first,
+                       unsigned long long n, int nv, unsigned long long* sizes, hipStream_t s);
+int tlagen_pack_states(const unsigned int* words, const unsigned long long* offs, unsigned long long first, unsigned long long n,
+                       const unsigned long long* at, unsigned int* out, hipStream_t s);
 
 namespace {
 
@@ -286,6 +291,8 @@ struct TlagenBackend : Backend {
         // entries): when it does not fit, the event the first search found is still reported
         RunOpts o1 = o;
         o1.workers = 1;
+        o1.recover_path.clear();      // a checkpoint of this search is in its order, not TLC's: start over
+        o1.checkpoint_path.clear();
         const std::string found = workers_event_;
         rc = run_once(o1, r, err, again);
         if (rc == 0 && r.verdict == MC_VERDICT_CAPACITY_OVERFLOW && !arena_overflow)
@@ -303,10 +310,9 @@ struct TlagenBackend : Backend {
     again = false;
     arena_overflow = false;
     const auto t_start = std::chrono::steady_clock::now();
-    if (!o.checkpoint_path.empty() || !o.recover_path.empty()) {
-      err = "checkpoint / recover are not implemented on the generated path";
-      return MC_E_UNSUPPORTED;
-    }
+    // TLC -checkpoint / -recover: the levels' states every checkpoint_every levels
+    // to checkpoint_path; the search continued from recover_path's
+    const bool saving = o.checkpoint_every > 0 && !o.checkpoint_path.empty(), recovering = !o.recover_path.empty();
     if (!o.disjunct_copies) {   // the generated code enumerates disjuncts as TLC does (MC_COMPAT_DISJUNCT_COPIES)
       err = "the generated path counts TLC's disjunct copies; MC_COMPAT_DISJUNCT_COPIES cannot be cleared on it";
       return MC_E_UNSUPPORTED;
@@ -357,6 +363,8 @@ struct TlagenBackend : Backend {
     HIPOK(hipModuleGetFunction(&f_keys, sc.mod, "tlg_keys_k"));
     HIPOK(hipModuleGetFunction(&f_mat, sc.mod, "tlg_mat_k"));
     HIPOK(hipModuleGetFunction(&f_stop, sc.mod, "tlg_stop_k"));
+    hipFunction_t f_rebuild = nullptr;
+    if (recovering) HIPOK(hipModuleGetFunction(&f_rebuild, sc.mod, "tlg_rebuild_k"));
     // HBM layout: store words + per-state offsets/parents/actions, seen-set, lanes' arenas (+ FIFO:
     // the level's inserted entries and their keys, unsorted and sorted)
     const u64 store = o.state_store_bytes ? o.state_store_bytes : (16ull << 30);
@@ -428,11 +436,28 @@ struct TlagenBackend : Backend {
     auto set_ctr = [&](u32 k, u64 v) -> int { HIPOK(hipMemcpy(d_ctr + k, &v, 8, hipMemcpyHostToDevice)); return 0; };
     r = RunResult();
     r.action_names = meta.actions;
-    if (int rc = launch(f_init, 1, 64)) return rc;
-    u64 first = 0, count = h[nctr - 2], gen_prev = h[C_GEN];
-    r.generated = (int64_t)h[C_GEN];
-    if (count) { r.depth = 1; r.levels.push_back({(int64_t)count, (int64_t)h[C_GEN], 0}); }
     const u64 grid = lanes / 64;
+    u64 first = 0, count = 0;
+    double t_load = 0;
+    if (!recovering) {
+      if (int rc = launch(f_init, 1, 64)) return rc;
+      count = h[nctr - 2];
+      r.generated = (int64_t)h[C_GEN];
+      if (count) { r.depth = 1; r.levels.push_back({(int64_t)count, (int64_t)h[C_GEN], 0}); }
+    } else {
+      // the file's states, counters and BFS position instead of Init; then the seen-set from the
+      // states.  The restored levels come after the rebuild: its time is the run's, not a level's
+      std::vector<LevelStat> levels;
+      if (int rc = load_checkpoint(o.recover_path, fifo, a, h, levels, first, count, r, err)) return rc;
+      t_load = since() - t_setup;
+      if (!h[C_CAP]) {
+        a.first = 0; a.count = h[nctr - 2];
+        if (int rc = launch(f_rebuild, grid, 64)) return rc;
+        if (h[C_ERR]) return ckpt::Reader(o.recover_path).other_model(err);   // a stored state is none of this model's
+      }
+      r.levels = levels;
+    }
+    u64 gen_prev = h[C_GEN];
     u64 fifo_ev = ~0ull;                              // FIFO: the stop point's event word
     std::vector<int64_t> prior_gen(nact, 0), prior_dist(nact, 0);
     int64_t prior_generated = 0;
@@ -477,8 +502,15 @@ struct TlagenBackend : Backend {
       gen_prev = h[C_GEN];
       first += count; count = fresh;
       if (fresh) ++r.depth; else r.levels.pop_back();
+      // a completed, non-empty level; never after an overflow (the last good file stays) nor with a
+      // -workers N event claimed (its level is cut short)
+      if (saving && fresh && !h[C_CAP] && !h[C_FLAG] && r.depth % o.checkpoint_every == 0)
+        if (int rc = save_checkpoint(o.checkpoint_path, fifo, a, h, lanes, first, count, r, err)) return rc;
     }
     const double t_loop = since();
+    if (timing && recovering)
+      std::fprintf(stderr, "tlagen timing: recover read + upload %.3f s, %llu states, %llu words\n", t_load,
+                   (unsigned long long)h[nctr - 2], (unsigned long long)h[nctr - 1]);
     if (timing)
       std::fprintf(stderr, "tlagen timing: code object %.3f s, module load + allocation + clears %.3f s, level loop %.3f s "
                            "(kernels %.3f s), store %.1f GiB, arena %.1f GiB\n", t_co, t_setup - t_co, t_loop - t_setup,
@@ -632,6 +664,120 @@ struct TlagenBackend : Backend {
         break;
     }
     (void)err;
+    return 0;
+  }
+
+  // ---------------------------------------------------------------- checkpoint / recover
+  // ckpt::GenHead around the shared framing (ckpt_file.h).  What names the model in the file: the
+  // code object's key (the generated source and its compile options, so every constant of the cfg)
+  // and the variable and action names; not where the module lay.
+  std::string ckpt_desc() const {
+    std::string d = "tlagen " + key + " variables";
+    for (auto& v : meta.vars) d += " " + v;
+    d += " actions";
+    for (auto& x : meta.actions) d += " " + x;
+    return d;
+  }
+  static constexpr u64 kCkptChunkBytes = 256ull << 20;   // host staging of a save or a load
+
+  // The store after a completed level.  The states' words go out packed in id order (tlagen_sort.hip);
+  // the lanes' arenas and handle stacks, idle between levels, are the device staging, so a save
+  // allocates nothing on the device and stages kCkptChunkBytes on the host whatever the store holds.
+  int save_checkpoint(const std::string& path, bool fifo, const KArgs& a, const std::vector<u64>& h, u64 lanes, u64 level_begin,
+                      u64 level_count, const RunResult& r, std::string& err) {
+    const size_t nctr = h.size();
+    const int nact = (int)meta.actions.size(), nv = (int)meta.vars.size();
+    const u64 total = h[nctr - 2], used = h[nctr - 1];
+    const std::string desc = ckpt_desc();
+    ckpt::GenHead g;
+    std::memset(&g, 0, sizeof g);
+    std::memcpy(g.magic, "RAFTMCG1", 8);
+    g.nwp = 0; g.total = total; g.level_begin = level_begin; g.level_count = level_count; g.seed = a.seed;
+    g.words = used; g.fifo = fifo ? 1 : 0;
+    g.generated = (int64_t)h[C_GEN]; g.distinct = (int64_t)total; g.depth = r.depth; g.generated_in_model = (int64_t)h[C_GIN];
+    g.n_act = nact; g.n_levels = (int64_t)r.levels.size(); g.desc_len = (int64_t)desc.size();
+    std::vector<int64_t> act_generated(nact), act_distinct(nact);
+    for (int k = 0; k < nact; ++k) { act_generated[k] = (int64_t)h[C_ACT + k]; act_distinct[k] = (int64_t)h[C_ACT + nact + k]; }
+    u64* d_at = (u64*)a.hstack;                                                 // sizes, then offsets, of a chunk of states
+    const u64 at_cap = std::min<u64>(1u << 20, lanes * a.hcap / 2 - 1);          // states per chunk
+    const u64 stage_words = std::min<u64>(lanes * a.acap, kCkptChunkBytes / 4);  // packed words per chunk (>= a state: it fits a lane's arena)
+    std::string why;
+    auto body = [&](FILE* f) -> bool {
+      std::vector<u64> buf(std::max<u64>(std::min(at_cap, total) + 1, std::min<u64>(kCkptChunkBytes / 8, std::max<u64>(total, (used + 1) / 2))));
+      auto sizes = [&](u64 i0, u64 n) -> bool {   // buf[0, n) = words of the states [i0, i0 + n)
+        if (tlagen_state_sizes(a.words, used, a.offs, i0, n, nv, d_at, 0) ||
+            hipMemcpy(buf.data(), d_at, n * 8, hipMemcpyDeviceToHost) != hipSuccess) { why = "reading the store failed"; return false; }
+        for (u64 k = 0; k < n; ++k) if (buf[k] == 0 || buf[k] > stage_words) { why = "a stored state is malformed"; return false; }
+        return true;
+      };
+      u64 at = 0;   // offs: where each state begins in the packed words
+      for (u64 i0 = 0; i0 < total; i0 += at_cap) {
+        const u64 n = std::min(at_cap, total - i0);
+        if (!sizes(i0, n)) return false;
+        for (u64 k = 0; k < n; ++k) { const u64 s = buf[k]; buf[k] = at; at += s; }
+        if (std::fwrite(buf.data(), 8, n, f) != n) return false;
+      }
+      if (at != used) { why = "the stored states do not add up to the stored words"; return false; }
+      for (int kind = 1; kind <= 2; ++kind) {   // parent, act
+        const size_t esz = kind == 1 ? 8 : 4;
+        const u64 per = kCkptChunkBytes / esz;
+        for (u64 i0 = 0; i0 < total; i0 += per) {
+          const u64 n = std::min(per, total - i0);
+          const void* src = kind == 1 ? (const void*)(a.parent + i0) : (const void*)(a.act + i0);
+          if (hipMemcpy(buf.data(), src, n * esz, hipMemcpyDeviceToHost) != hipSuccess) { why = "reading the store failed"; return false; }
+          if (std::fwrite(buf.data(), esz, n, f) != n) return false;
+        }
+      }
+      for (u64 i0 = 0; i0 < total;) {   // words: as many states as the staging holds at a time
+        const u64 n = std::min(at_cap, total - i0);
+        if (!sizes(i0, n)) return false;
+        u64 take = 0, w = 0;
+        for (; take < n && w + buf[take] <= stage_words; ++take) { const u64 s = buf[take]; buf[take] = w; w += s; }
+        buf[take] = w;
+        if (hipMemcpy(d_at, buf.data(), (take + 1) * 8, hipMemcpyHostToDevice) != hipSuccess ||
+            tlagen_pack_states(a.words, a.offs, i0, take, d_at, a.arena, 0) ||
+            hipMemcpy(buf.data(), a.arena, w * 4, hipMemcpyDeviceToHost) != hipSuccess) { why = "reading the store failed"; return false; }
+        if (std::fwrite(buf.data(), 4, w, f) != w) return false;
+        i0 += take;
+      }
+      return true;
+    };
+    const int rc = ckpt::write_file(path, g, desc, act_generated, act_distinct, r.levels, body, err);
+    if (rc && !why.empty()) err += " (" + why + ")";
+    return rc;
+  }
+
+  // The file into the store and the counters (h, and the device's); first / count: the level the
+  // search goes on with.  A file that does not fit this run's store sets C_CAP in h alone and loads
+  // nothing: the run ends as a capacity overflow, as a search that outgrew the store does.
+  int load_checkpoint(const std::string& path, bool fifo, KArgs& a, std::vector<u64>& h, std::vector<LevelStat>& levels, u64& first,
+                      u64& count, RunResult& r, std::string& err) {
+    const size_t nctr = h.size();
+    const int nact = (int)meta.actions.size();
+    ckpt::GenHead g;
+    ckpt::Reader in(path);
+    std::vector<int64_t> act_generated, act_distinct;
+    if (int rc = in.head("RAFTMCG1", 0, nact, ckpt_desc(), g, act_generated, act_distinct, levels, err)) return rc;
+    if (int rc = ckpt::check_gen_head(in, g, levels, err)) return rc;
+    if (fifo && !g.fifo) {
+      err = "checkpoint " + path + " was written by a -workers N search: its kept parents are not TLC's single-worker "
+            "FIFO ones, so it cannot resume a -workers 1 search";
+      return MC_E_INVALID;
+    }
+    r.depth = g.depth;
+    first = g.level_begin; count = g.level_count;
+    a.seed = g.seed;
+    if (g.total > a.states_cap || g.words > a.words_cap) { h[C_CAP] = 1; return 0; }
+    auto upload = [&](int kind, const void* data, uint64_t i0, uint64_t n, std::string& e) -> int {
+      void* dst = kind == 0 ? (void*)(a.offs + i0) : kind == 1 ? (void*)(a.parent + i0) : kind == 2 ? (void*)(a.act + i0) : (void*)(a.words + i0);
+      if (hipMemcpy(dst, data, n * (kind < 2 ? 8 : 4), hipMemcpyHostToDevice) != hipSuccess) { e = "uploading checkpoint " + path + " failed"; return MC_E_NO_DEVICE; }
+      return 0;
+    };
+    if (int rc = ckpt::read_gen_body(in, g, (uint64_t)levels.front().states, kCkptChunkBytes, upload, err)) return rc;
+    h[C_GEN] = (u64)g.generated; h[C_GIN] = (u64)g.generated_in_model;
+    for (int k = 0; k < nact; ++k) { h[C_ACT + k] = (u64)act_generated[k]; h[C_ACT + nact + k] = (u64)act_distinct[k]; }
+    h[nctr - 1] = g.words; h[nctr - 2] = g.total; h[nctr - 3] = g.total;
+    if (hipMemcpy(a.ctr, h.data(), nctr * 8, hipMemcpyHostToDevice) != hipSuccess) { err = "counter write failed"; return MC_E_NO_DEVICE; }
     return 0;
   }
 

@@ -130,6 +130,23 @@ __device__ inline bool insert_plain(Args& a, unsigned long long fp) {
   }
 }
 
+// A state's seen-set fingerprint, for the search (Em) and for the rebuild of the seen-set from the
+// stored states on recovery (tlg_rebuild_k): both go through these, so a recovered table holds what
+// the search put there.  With a VIEW or SYMMETRY it is fp_words over the words of tlg::canon_view
+// of the state (A.err set: not evaluated); otherwise the sum over the variables of fp_term, closed
+// by fp_of_terms.  A variable's term is a function of its canonical words alone, wherever they lie.
+__device__ inline unsigned long long fp_term(const u32* w, int v, unsigned long long seed) {
+  return fp_words(w, w[0] >> 3, seed ^ (0x9E3779B97F4A7C15ull * (unsigned long long)(v + 1)));
+}
+__device__ inline unsigned long long fp_of_terms(unsigned long long sum, unsigned long long seed) {
+  const unsigned long long s = fmix(sum ^ seed);
+  return s ? s : 1ull;
+}
+__device__ inline unsigned long long fp_of_view(Ar& A, tlg::Cx& d, unsigned long long seed) {
+  const u32 vh = tlg::canon_view(d);
+  return A.err ? 0ull : fp_words(A.w + vh, sz(A, vh), seed);
+}
+
 struct Em {
   Args* a;
   u32 mode;
@@ -190,9 +207,8 @@ struct Em {
       ++gin;
       unsigned long long fp;
       if (tlg::HAS_VIEW || tlg::HAS_SYMMETRY) {   // TLC's VIEW / SYMMETRY: the fingerprint of what tells states apart
-        const u32 vh = tlg::canon_view(d);
+        fp = fp_of_view(A, d, a->seed);
         if (A.err) { error_event(A, key, keyed); A.top = t0; return; }
-        fp = fp_words(A.w + vh, sz(A, vh), a->seed);
       } else {
         fp = state_fp(A, c, chg);
       }
@@ -226,17 +242,14 @@ struct Em {
     A.top = t0;
   }
 
-  // a state's fingerprint: the sum of per-variable terms (fp_words of the variable's canonical
-  // words under a per-variable seed), mixed; a variable the successor left unchanged reuses the
-  // parent's term, so only changed variables are read and hashed
-  __device__ static unsigned long long var_term(const Ar& A, u32 h, int v, unsigned long long seed) {
-    return fp_words(A.w + h, sz(A, h), seed ^ (0x9E3779B97F4A7C15ull * (unsigned long long)(v + 1)));
-  }
+  // a state's fingerprint: the sum of per-variable terms (fp_term: fp_words of the variable's
+  // canonical words under a per-variable seed), mixed; a variable the successor left unchanged
+  // reuses the parent's term, so only changed variables are read and hashed
+  __device__ static unsigned long long var_term(const Ar& A, u32 h, int v, unsigned long long seed) { return fp_term(A.w + h, v, seed); }
   __device__ unsigned long long state_fp(const Ar& A, tlg::Cx& c, unsigned long long chg) const {
     unsigned long long s = 0;
     for (int i = 0; i < tlg::NV; ++i) s += ((chg >> i) & 1ull) ? var_term(A, c.nxt[i], i, a->seed) : ph[i];
-    s = fmix(s ^ a->seed);
-    return s ? s : 1ull;
+    return fp_of_terms(s, a->seed);
   }
   __device__ void parent_terms(const Ar& A, tlg::Cx& c) {
     for (int i = 0; i < tlg::NV; ++i) ph[i] = var_term(A, c.cur[i], i, a->seed);
@@ -423,6 +436,74 @@ extern "C" __global__ void __launch_bounds__(64) tlg_mat_k(tlk::Args a) {
     (void)tlk::expand_state(a, A, c, em, floor, a.first + r);
   }
   em.flush();
+}
+
+// Recovery from a checkpoint (TLC -recover): the fingerprints of the stored states [first, first +
+// count) go back into the cleared seen-set; the file holds states, not the table, so the table may
+// be of another size than the writer's.  With a VIEW or SYMMETRY the state is copied into the lane's
+// arena (as expand_state does) for canon_view; otherwise the variables' terms are hashed where they
+// lie in the store (tlv::copy_in is a verbatim copy of the canonical words, so the term is the
+// same).  FIFO entries get the complement of key 0, all ones: no later insert_keyed changes them,
+// and no pass reads an older level's key (tlg_keys_k reads this level's newpos entries).  A
+// fingerprint met twice among the stored states is a collision the search had too: not counted.
+// A state that runs past the stored words or whose view cannot be evaluated is no state of this
+// model: its error bits go to C_ERR (the host refuses the file); E_OVF is the arena's (C_CAP 4).
+namespace tlk {
+// (out of line, with the arguments behind a reference as the search's lanes have them in Em: the
+// kernel reads its argument block once, up front, before any of the stores below)
+__device__ __attribute__((noinline)) void rebuild_states(Args& a) {
+  const unsigned long long lane = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
+  constexpr bool viewed = tlg::HAS_VIEW || tlg::HAS_SYMMETRY;
+  tlv::Ar A;
+  tlg::Cx c;
+  if (viewed) {
+    tlv::init(A, a.arena + lane * a.acap, a.acap, a.hstack + lane * a.hcap, a.hcap);
+    c.A = &A;
+    tlg::init_consts(c);
+  }
+  const tlv::u32 floor = viewed ? A.top : 0u;
+  const unsigned long long used = __atomic_load_n(a.words_used, __ATOMIC_RELAXED);   // (a vector load: ordered with the stores below)
+  for (unsigned long long i = lane; i < a.count; i += stride) {
+    if (__atomic_load_n(&a.ctr[tlk::C_CAP], __ATOMIC_RELAXED)) break;
+    unsigned long long q = a.offs[a.first + i];
+    // the variables' extents: each header's length within the stored words
+    unsigned long long at[tlg::NV > 0 ? tlg::NV : 1];
+    bool ok = true;
+    for (int v = 0; v < tlg::NV; ++v) {
+      const unsigned long long n = q < used ? (unsigned long long)(a.words[q] >> 3) : 0ull;
+      if (n == 0 || n > used - q) { ok = false; break; }
+      at[v] = q;
+      q += n;
+    }
+    if (!ok) { atomicOr(&a.ctr[tlk::C_ERR], (unsigned long long)tlv::E_TYPE); continue; }
+    unsigned long long fp;
+    if (viewed) {
+      A.top = floor; A.htop = 0; A.err = 0;
+      for (int v = 0; v < tlg::NV; ++v) c.cur[v] = tlv::copy_in(A, a.words + at[v]);
+      fp = (A.err & tlv::E_OVF) ? 0ull : tlk::fp_of_view(A, c, a.seed);
+      if (A.err) {
+        if (A.err & tlv::E_OVF) atomicOr(&a.ctr[tlk::C_CAP], 4ull);
+        else atomicOr(&a.ctr[tlk::C_ERR], (unsigned long long)A.err);
+        continue;
+      }
+    } else {
+      unsigned long long s = 0;
+      for (int v = 0; v < tlg::NV; ++v) s += tlk::fp_term(a.words + at[v], v, a.seed);
+      fp = tlk::fp_of_terms(s, a.seed);
+    }
+    if (a.fifo) {
+      unsigned long long pos = 0;
+      (void)tlk::insert_keyed(a, fp, 0ull, pos);
+    } else {
+      (void)tlk::insert_plain(a, fp);
+    }
+  }
+}
+}  // namespace tlk
+
+extern "C" __global__ void __launch_bounds__(64) tlg_rebuild_k(tlk::Args a) {
+  tlk::rebuild_states(a);
 }
 
 // the stop point: parents [0, stop_rank] of the level re-expanded for TLC's generated counts
