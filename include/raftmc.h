@@ -69,7 +69,11 @@ extern "C" {
  * variable tuple (history included) under TLC's value order, then the VIEW of that state.  Set by
  * mc_default_opts (the drop-in default: TLC's counts for a cfg with SYMMETRY, tlc_membership/raft.cfg:29-30);
  * cleared, SYMMETRY + VIEW identify states whose VIEWs lie in one orbit (the opt-in "orbit" mode,
- * CLI -symmetry orbit: faster, fewer distinct states when histories differ).  tlc_membership only. */
+ * CLI -symmetry orbit: faster, fewer distinct states when histories differ).  tlc_membership only.
+ * raft_original accepts `SYMMETRY Name` with Name == Permutations(Server) (configs/raft_original_sym_mc.tla):
+ * it has no VIEW, so both rules give one partition and this flag has no effect there.  Its seen-set keeps
+ * one fingerprint per orbit, the kept and printed states are successors as generated; single GPU only
+ * (n_gpus > 1, mc_shard_* and count_final_level: MC_E_UNSUPPORTED).  DESIGN.md §11. */
 #define MC_COMPAT_SYM_TLC 0x2u
 /* TLC's getNextStates enumerates every true disjunct of a disjunctive guard inside an action as a branch
  * of its own, so the one successor such a guard admits is GENERATED once per true disjunct
@@ -217,7 +221,8 @@ int mc_collision_observed(mc_ctx* ctx, double* val);
  * NULL or 0 disables.  mc_set_recover: the next mc_run resumes from `path` instead of Init
  * (the seen-set is rebuilt on the GPU from the stored states); generated/distinct/depth/per-action
  * counts continue exactly; kernel timings cover the resumed part.  A checkpoint of another
- * model or of another backend (or of the other SYMMETRY mode, or — raft_original and the generated
+ * model or of another backend (or of the other SYMMETRY mode, or — raft_original — of a search with
+ * SYMMETRY for one without it and the reverse, or — raft_original and the generated
  * path — a -workers N checkpoint for a -workers 1 search: its kept parents are not TLC's; a
  * -workers 1 checkpoint does resume a -workers N search) is refused (MC_E_INVALID), a truncated or
  * unreadable file MC_E_IO.  fp_table_bytes and state_store_bytes may be larger on recovery than when

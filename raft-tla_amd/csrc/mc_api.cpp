@@ -25,6 +25,7 @@ struct mc_ctx {
   rmc::RunResult res;
   bool ran = false;
   bool released = false;   // mc_release_device_memory since the last run
+  bool orig_sym = false;   // raft_original under SYMMETRY Permutations(Server): one GPU, mc_run only
   std::string last_error, tla_path, cfg_path;
   mutable std::map<std::string, std::string> action_loc;   // action name -> TLC location text ("" if none)
   const std::string& location_of(const std::string& act) const {
@@ -150,11 +151,19 @@ int mc_open(const char* tla_path, const char* cfg_path, const mc_opts* o, mc_ctx
       catch (const rmc::CfgError&) { if (o->frontend == MC_FRONTEND_HAND) throw; fam = "tlagen"; }
     }
     rmc::CfgFile cfg = rmc::parse_cfg_text(rmc::read_text_file(cfg_path));
+    if (!cfg.symmetry.empty()) cfg.symmetry_def = rmc::definition_text(tla_path, cfg.symmetry);
     // count_final_level exists for raft_original's -workers N search with a depth bound (single GPU
     // or sharded): anywhere else it would be silently ignored, so it is refused
     if (o->count_final_level && (fam != "raft_original" || o->workers == 1 || o->max_depth <= 0))
       throw rmc::CfgError(MC_E_UNSUPPORTED, "count_final_level needs thirdparty/raft_original.tla (hand-compiled), workers != 1 "
                                             "and max_depth > 0");
+    // raft_original under SYMMETRY: orbit fingerprints exist on the single-GPU pipeline only (DESIGN.md
+    // §11); every other mode refuses rather than search without the symmetry
+    c->orig_sym = fam == "raft_original" && !cfg.symmetry.empty();
+    if (c->orig_sym && c->n_gpus > 1)
+      throw rmc::CfgError(MC_E_UNSUPPORTED, "SYMMETRY for raft_original runs on one GPU (n_gpus = 1): the sharded search has no orbit fingerprints");
+    if (c->orig_sym && o->count_final_level)
+      throw rmc::CfgError(MC_E_UNSUPPORTED, "SYMMETRY for raft_original: not with count_final_level");
     if (fam == "tlagen" && c->n_gpus > 1) throw rmc::CfgError(MC_E_UNSUPPORTED, "the generated path runs on one GPU (n_gpus = 1)");
     auto make = [&]() -> rmc::Backend* {
       if (fam == "raft_original") return rmc::make_orig_backend(cfg);
@@ -565,6 +574,10 @@ int mc_exit_code(const mc_ctx* c) {
   if (c->ro.continue_mode) { \
     c->last_error = "continue mode runs on one GPU (mc_run); a sharded run cannot use it"; \
     return MC_E_UNSUPPORTED; \
+  } \
+  if (c->orig_sym) { \
+    c->last_error = "SYMMETRY for raft_original runs on one GPU (mc_run); the sharded search has no orbit fingerprints"; \
+    return MC_E_UNSUPPORTED; \
   }
 #define SHARD_RC(expr)                      \
   do {                                      \
@@ -713,6 +726,10 @@ int mc_shard_run_loopback(mc_ctx* const* ctxs, int32_t world) {
     }
     if (ctxs[r]->ro.continue_mode) {
       ctxs[r]->last_error = "continue mode runs on one GPU (mc_run); a sharded run cannot use it";
+      return MC_E_UNSUPPORTED;
+    }
+    if (ctxs[r]->orig_sym) {
+      ctxs[r]->last_error = "SYMMETRY for raft_original runs on one GPU (mc_run); the sharded search has no orbit fingerprints";
       return MC_E_UNSUPPORTED;
     }
   }

@@ -34,6 +34,9 @@ struct CfgFile {
   std::vector<std::pair<std::string, CVal>> constants;
   std::vector<std::pair<std::string, std::string>> overrides;
   std::string init, next, symmetry, view;
+  // the body of the SYMMETRY name's definition in the root module or a module it EXTENDS, blanks and
+  // comments removed ("" = no such definition); filled by mc_open (tla_value.h definition_text)
+  std::string symmetry_def;
   std::vector<std::string> constraints, action_constraints, invariants, properties;
   bool has(const std::string& n) const;
   const CVal& get(const std::string& n) const;

@@ -1385,6 +1385,7 @@ __global__ void __launch_bounds__(BS) orig_reinsert(const u32* states, u64 n, u6
 }
 
 #include "orig_sim.hip"   // simulation mode: the walker kernel and the host replay of one walk
+#include "orig_sym.hip"   // SYMMETRY Permutations(Server): the orbit-fingerprint generate and reinsert kernels
 
 }  // namespace rmc
 #include "dev_owner.h"   // host only, included here so that the device code above keeps its text
@@ -1424,7 +1425,11 @@ class OrigGpu : public Backend {
     for (size_t k = 0; k < m_.inv_names.size(); ++k) o << (k ? ", " : "") << "\"" << m_.inv_names[k] << "\"";
     o << "], \"actions\": [";
     for (int k = 0; k < OA_NACT; ++k) o << (k ? ", " : "") << "\"" << kOrigActNames[k] << "\"";
-    o << "]}";
+    o << "]";
+    // only under SYMMETRY (the description is also the checkpoint's model identity: a symmetric file
+    // does not resume an unsymmetric search, nor the reverse, and unsymmetric files stay as they were)
+    if (m_.rt.symmetry) o << ", \"symmetry\": true, \"permutations\": " << S::NPERM;
+    o << "}";
     return o.str();
   }
 
@@ -1530,6 +1535,10 @@ class OrigGpu : public Backend {
   // device); K_LEAD must be zero before (level start: orig_reset_ctr, later chunks: orig_advance, or
   // on a pipelined level the generate stream's own re-arm)
   void launch_generate(const GenArgs& g, unsigned nblk, hipStream_t st) {
+    if (m_.rt.symmetry) {   // orbit fingerprints, every instance in one kernel (orig_sym.hip)
+      hipLaunchKernelGGL((orig_generate_sym<S>), dim3(nblk), dim3(BS), 0, st, g);
+      return;
+    }
     hipLaunchKernelGGL((orig_generate<S>), dim3(nblk), dim3(BS), 0, st, g);
     const unsigned lblk = std::min<unsigned>(nblk, std::max<unsigned>(64u, nblk / 8));
     hipLaunchKernelGGL((orig_generate_lead<S>), dim3(lblk), dim3(BS), 0, st, g);
@@ -1838,7 +1847,8 @@ class OrigGpu : public Backend {
   // Set up, then per level: spill?, switch to the full table?, queue the level's kernels, read its
   // counters back (the level's one host wait), decide.
   int run(const RunOpts& o, RunResult& r, std::string& err) override {
-    if (o.sim_walks > 0) return simulate(o, r, err);   // TLC -simulate: random walks, not a BFS
+    if (o.sim_walks > 0) return simulate(o, r, err);   // TLC -simulate: random walks, not a BFS (no fingerprints: SYMMETRY is ignored)
+    if (m_.rt.symmetry && o.count_final_level) { err = "SYMMETRY for raft_original: not with count_final_level"; return MC_E_UNSUPPORTED; }
     unstored_ = 0;   // a previous run's unstored level must not outlive it (mc_dump_states)
     if (int rc = ensure_alloc(o, 0, err)) return rc;   // world 0 = single-GPU pipeline
     Search s;
@@ -1966,7 +1976,7 @@ class OrigGpu : public Backend {
     W s0; S::init(s0);
     u32 w0[S::NW]; S::pack(s0, w0);
     InitWords<NWP> wp = {}; for (int q = 0; q < S::NW; ++q) wp.w[q] = w0[q];
-    const u64 fp0 = fp64(w0, r.seed);
+    const u64 fp0 = m_.rt.symmetry ? S::fp_sym(s0, r.seed) : fp64(w0, r.seed);
     static_assert(NWP <= 64, "orig_init_state: one lane per state word");
     if (s.fifo) hipLaunchKernelGGL((orig_init_state<NWP, 2>), dim3(1), dim3(64), 0, stream_, wp, store_.states(), store_.meta(), s.tbl, s.tmask, fp0);
     else hipLaunchKernelGGL((orig_init_state<NWP, 1>), dim3(1), dim3(64), 0, stream_, wp, store_.states(), store_.meta(), s.tbl, s.tmask, fp0);
@@ -2332,7 +2342,11 @@ class OrigGpu : public Backend {
     }
     auto reinsert = [&](const u32* states, u64 n) {
       const dim3 grid((unsigned)((n + BS - 1) / BS));
-      if (last_fifo_)
+      if (m_.rt.symmetry && last_fifo_)
+        hipLaunchKernelGGL((orig_reinsert_sym<S, 2>), grid, dim3(BS), 0, stream_, states, n, d_table_, table_mask_, (u64)h.seed, (unsigned long long*)d_ctr_);
+      else if (m_.rt.symmetry)
+        hipLaunchKernelGGL((orig_reinsert_sym<S, 1>), grid, dim3(BS), 0, stream_, states, n, d_table_, 2 * table_mask_ + 1, (u64)h.seed, (unsigned long long*)d_ctr_);
+      else if (last_fifo_)
         hipLaunchKernelGGL((orig_reinsert<S, 2>), grid, dim3(BS), 0, stream_, states, n, d_table_, table_mask_, (u64)h.seed, (unsigned long long*)d_ctr_);
       else
         hipLaunchKernelGGL((orig_reinsert<S, 1>), grid, dim3(BS), 0, stream_, states, n, d_table_, 2 * table_mask_ + 1, (u64)h.seed, (unsigned long long*)d_ctr_);
@@ -2354,6 +2368,7 @@ class OrigGpu : public Backend {
   // ================================================================ sharded mode
   int shard_open(const RunOpts& o, int rank, int world, std::string& err) override {
     if (world < 1 || world > 8 || rank < 0 || rank >= world) { err = "sharded mode supports 1..8 ranks"; return MC_E_INVALID; }
+    if (m_.rt.symmetry) { err = "SYMMETRY for raft_original runs on one GPU (mc_run); the sharded search has no orbit fingerprints"; return MC_E_UNSUPPORTED; }
     if (int rc = ensure_alloc(o, world, err)) return rc;
     rank_ = rank; world_ = world; sopts_ = o;
     unstored_ = 0;

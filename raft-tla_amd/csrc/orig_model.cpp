@@ -37,7 +37,20 @@ OrigModel resolve_orig_model(const CfgFile& cfg) {
     throw CfgError(MC_E_UNSUPPORTED, "message count range must lie within -7..6");
   if (cfg.init != "Init") throw CfgError(MC_E_UNSUPPORTED, "INIT must be Init");
   if (cfg.next != "Next") throw CfgError(MC_E_UNSUPPORTED, "NEXT must be Next (raft_original.tla:453)");
-  if (!cfg.symmetry.empty() || !cfg.view.empty()) throw CfgError(MC_E_UNSUPPORTED, "SYMMETRY/VIEW are not supported for raft_original in this build");
+  if (!cfg.view.empty())
+    throw CfgError(MC_E_UNSUPPORTED, "VIEW " + cfg.view + " is not supported for raft_original: the seen-set fingerprints the full state "
+                                     "(or, with SYMMETRY, its orbit under Permutations(Server))");
+  if (!cfg.symmetry.empty()) {
+    // SYMMETRY Name with Name == Permutations(Server) in the root module or a module it EXTENDS
+    const std::string& def = cfg.symmetry_def;
+    if (def.empty())
+      throw CfgError(MC_E_UNSUPPORTED, "SYMMETRY " + cfg.symmetry + ": the module and the modules it EXTENDS do not define " + cfg.symmetry +
+                                       " (configs/raft_original_sym_mc.tla defines ServerSymmetry == Permutations(Server))");
+    if (def != "Permutations(Server)")
+      throw CfgError(MC_E_UNSUPPORTED, "SYMMETRY " + cfg.symmetry + " == " + def + ": raft_original supports exactly Permutations(Server) "
+                                       "(no symmetry over Value, no union of permutation sets)");
+    m.rt.symmetry = 1;
+  }
   if (!cfg.action_constraints.empty()) throw CfgError(MC_E_UNSUPPORTED, "ACTION_CONSTRAINTS are not supported for raft_original");
   if (!cfg.properties.empty()) throw CfgError(MC_E_UNSUPPORTED, "temporal PROPERTIES are not supported");
   for (auto& c : cfg.constraints) {

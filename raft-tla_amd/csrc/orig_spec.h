@@ -57,7 +57,10 @@ struct OrigRuntime {
   int min_count, max_count;   // MinMsgCount..MaxMsgCount
   u32 constraints;            // OC_* mask
   u32 invariants;             // OI_* mask (cfg order kept on host)
+  u32 symmetry;               // 1 = SYMMETRY Permutations(Server): one seen-set entry per orbit (S::fp_sym)
 };
+
+constexpr int perm_count(int n) { return n <= 1 ? 1 : n * perm_count(n - 1); }   // |Permutations(Server)| = N!
 
 template <int N_, int NV_, int MT_, int ML_, int MK_>
 struct Orig {
@@ -814,6 +817,202 @@ struct Orig {
 #pragma unroll
     for (int k = 0; k < MK; ++k) { const u64 x = in.get(ENTB); t.bag.v[k] = x ? (BE)x : BEMPTY; }
     t.bag.v[MK] = BEMPTY;
+  }
+
+  // ---------------------------------------------------------------- SYMMETRY Permutations(Server)
+  // raft_original.tla treats servers interchangeably: Init, every action, every constraint and
+  // every invariant compiled here commute with a permutation of Server.  A permutation pi is a
+  // word of 3 bits per server, pi(i) = (pi >> 3i) & 7 = the image of server i.  Value is not
+  // permuted, so logs, log universe indices and allLogs are fixed by every pi.
+  static constexpr int NPERM = perm_count(N);
+  RMC_HD static int pi_of(u32 pi, int i) { return (int)((pi >> (3 * i)) & 7u); }
+  // the p-th permutation in Lehmer order, 0 <= p < N! (arithmetic only: no table)
+  RMC_HD static u32 perm_of(int p) {
+    u32 avail = 0x76543210u, pi = 0;
+    int rem = p;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+      const int f = perm_count(N - 1 - i), d = rem / f;
+      rem -= d * f;
+      pi |= ((avail >> (4 * d)) & 7u) << (3 * i);
+      avail = (avail & (u32)lomask(4 * d)) | ((avail >> (4 * (d + 1))) << (4 * d));
+    }
+    return pi;
+  }
+  RMC_HD static u32 perm_inverse(u32 pi) {
+    u32 inv = 0;
+#pragma unroll
+    for (int i = 0; i < N; ++i) inv |= (u32)i << (3 * pi_of(pi, i));
+    return inv;
+  }
+  // a server set (bit j = server j) / a row of N fields of WD bits indexed by server, under pi
+  RMC_HD static u32 perm_bits(u32 b, u32 pi) {
+    u32 r = 0;
+#pragma unroll
+    for (int j = 0; j < N; ++j) r |= ((b >> j) & 1u) << pi_of(pi, j);
+    return r;
+  }
+  template <int WD, class T>
+  RMC_HD static T perm_fields(T row, u32 pi) {
+    T r = 0;
+#pragma unroll
+    for (int j = 0; j < N; ++j) r |= (T)((row >> (j * WD)) & (T)lomask(WD)) << (pi_of(pi, j) * WD);
+    return r;
+  }
+  // a message code with msource / mdest renamed (their offsets per class: msrc, mdst)
+  RMC_HD static MC perm_msg(MC c, u32 pi) {
+    const int t = mtype(c);
+    const int so = TB + ((t == RVP || t == AEP) ? 1 : 0);
+    const int dofs = t == RVQ ? TB + SB + TB + CIB : t == RVP ? 1 + TB + SB + LIB : t == AEP ? TB + 1 + SB + CIB
+                                                                                              : TB + SB + TB + CIB + LIB + EB;
+    const MC m = (MC)lomask(SB);
+    const MC src = (MC)pi_of(pi, (int)((c >> so) & m)), dst = (MC)pi_of(pi, (int)((c >> dofs) & m));
+    return (MC)((c & ~(m << so) & ~(m << dofs)) | (src << so) | (dst << dofs));
+  }
+  RMC_HD static BE perm_entry(BE ent, u32 pi) {
+    return (BE)(((BE)perm_msg(ecode_of(ent), pi) << CNTB) | (ent & (BE)lomask(CNTB)));
+  }
+  // an election record with eleader renamed, evotes and the evoterLog cells moved (both layouts: a
+  // cell is EVB bits, with or without its presence bit; an absent cell is 0 in either)
+  RMC_HD static u64 perm_el(u64 rec, u32 pi) {
+    constexpr int OV = ETB + SB + LIB, OC = OV + N;
+    const u64 keep = rec & (lomask(ETB) | (lomask(LIB) << (ETB + SB)));
+    const u64 ldr = (u64)pi_of(pi, (int)((rec >> ETB) & lomask(SB)));
+    const u64 ev = (u64)perm_bits((u32)((rec >> OV) & lomask(N)), pi);
+    const u64 cells = perm_fields<EVB, u64>((rec >> OC) & lomask(N * EVB), pi);
+    return keep | (ldr << ETB) | (ev << OV) | (cells << OC);
+  }
+
+  // t = the image of s under pi: per-server fields moved to their new index, votedFor renamed (Nil
+  // fixed), vote sets / nextIndex / matchIndex / voterLog moved by row and by column, messages and
+  // election records renamed with the bag and the election set sorted again, allLogs kept.  The
+  // definition the fingerprint below is tested against (tests/native/orig_sym_host.cpp); not a hot path.
+  RMC_HD static void permute(const Work& s, u32 pi, Work& t) {
+    t.term = 0; t.st = 0; t.voted = 0; t.commit = 0; t.vresp = 0; t.vgrant = 0;
+#pragma unroll
+    for (int i = 0; i < N; ++i) { t.nexti.v[i] = 0; t.matchi.v[i] = 0; t.log.v[i] = 0; t.vl.v[i] = 0; }
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+      const int x = pi_of(pi, i), v = g_voted(s, i);
+      fset<TB>(t.term, x, fget<TB>(s.term, i));
+      fset<2>(t.st, x, fget<2>(s.st, i));
+      fset<VB>(t.voted, x, (u32)(v == N ? N : pi_of(pi, v)));
+      fset<CIB>(t.commit, x, fget<CIB>(s.commit, i));
+      set_row_bits(t.vresp, x, perm_bits(row_bits(s.vresp, i), pi));
+      set_row_bits(t.vgrant, x, perm_bits(row_bits(s.vgrant, i), pi));
+      put(t.nexti, x, perm_fields<NIB, u32>(s.nexti.v[i], pi));
+      put(t.matchi, x, perm_fields<CIB, u32>(s.matchi.v[i], pi));
+      put(t.log, x, s.log.v[i]);
+      put(t.vl, x, perm_fields<VLB, VR>(s.vl.v[i], pi));
+    }
+#pragma unroll
+    for (int k = 0; k < AW; ++k) t.allLogs[k] = s.allLogs[k];
+#pragma unroll
+    for (int k = 0; k < EMAX; ++k) t.el[k] = s.el[k] == EMPTY ? EMPTY : perm_el(s.el[k], pi);
+#pragma unroll
+    for (int a = 0; a < EMAX; ++a)
+#pragma unroll
+      for (int b = 0; b + 1 < EMAX - a; ++b) {
+        const u64 x = t.el[b], y = t.el[b + 1];
+        t.el[b] = x < y ? x : y; t.el[b + 1] = x < y ? y : x;
+      }
+#pragma unroll
+    for (int k = 0; k < MK + 1; ++k) t.bag.v[k] = s.bag.v[k] == BEMPTY ? BEMPTY : perm_entry(s.bag.v[k], pi);
+#pragma unroll
+    for (int a = 0; a < MK + 1; ++a)
+#pragma unroll
+      for (int b = 0; b + 1 < MK + 1 - a; ++b) {
+        const BE x = t.bag.v[b], y = t.bag.v[b + 1];
+        t.bag.v[b] = x < y ? x : y; t.bag.v[b + 1] = x < y ? y : x;
+      }
+  }
+
+  // 64-bit hash of pi(s) without building it: a sum of keyed mixes, one group per server keyed by
+  // the server's NEW index (its fields read through pi), one mix per election record and per bag
+  // entry (renamed; a sum is commutative, so neither set is sorted again).  Equal sums <=> equal
+  // permuted states, up to 2^-64 coincidences (allLogs, which no pi changes, is fp_sym's term).
+  static_assert(TB + 2 + VB + CIB + 2 * N <= 32 && TB + 3 + CIB + 8 <= 32, "sym_hash / fp_sym: a server's scalar fields share 32 bits");
+  RMC_HD static u64 sym_key(u64 seed, int slot) { return seed + (u64)(slot + 1) * P1; }
+  RMC_HD static u64 sym_hash(const Work& s, u32 pi, u64 seed) {
+    u64 acc = 0;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+      const int x = pi_of(pi, i), v = g_voted(s, i);
+      u32 sc = fget<TB>(s.term, i);
+      sc |= fget<2>(s.st, i) << TB;
+      sc |= (u32)(v == N ? N : pi_of(pi, v)) << (TB + 2);
+      sc |= fget<CIB>(s.commit, i) << (TB + 2 + VB);
+      sc |= perm_bits(row_bits(s.vresp, i), pi) << (TB + 2 + VB + CIB);
+      sc |= perm_bits(row_bits(s.vgrant, i), pi) << (TB + 2 + VB + CIB + N);
+      const u64 w0 = (u64)sc | ((u64)s.log.v[i] << 32);
+      const u64 w1 = (u64)perm_fields<NIB, u32>(s.nexti.v[i], pi) | ((u64)perm_fields<CIB, u32>(s.matchi.v[i], pi) << 32);
+      const u64 w2 = (u64)perm_fields<VLB, VR>(s.vl.v[i], pi);
+      acc += fmix64(w0 ^ sym_key(seed, 3 * x)) + fmix64(w1 ^ sym_key(seed, 3 * x + 1)) + fmix64(w2 ^ sym_key(seed, 3 * x + 2));
+    }
+#pragma unroll
+    for (int k = 0; k < EMAX; ++k)
+      if (s.el[k] != EMPTY) acc += fmix64(perm_el(s.el[k], pi) ^ sym_key(seed, 3 * N));
+#pragma unroll
+    for (int k = 0; k < MK + 1; ++k)
+      if (s.bag.v[k] != BEMPTY) acc += fmix64((u64)perm_entry(s.bag.v[k], pi) ^ sym_key(seed, 3 * N + 1));
+    return acc;
+  }
+
+  // One fingerprint per orbit of Permutations(Server): the minimum of sym_hash over candidate
+  // permutations.  A per-server signature that no permutation changes (term, state, commitIndex,
+  // votedFor = Nil, the sizes of both vote sets, the log) orders the servers; the candidates are
+  // the permutations that send every server into the index range of its signature class, so only
+  // servers of equal signature are permuted among themselves.  For pi(s) those are the candidates
+  // of s composed with pi^-1: the minimum runs over the same set of permuted states, whichever
+  // member of the orbit it starts from.  All signatures distinct (the common case once servers
+  // diverge): one permutation.  Never 0 (the seen-set's empty marker).
+  RMC_HD static u64 fp_sym(const Work& s, u64 seed) {
+    u64 base = 0;
+#pragma unroll
+    for (int k = 0; k < AW; ++k) base += fmix64(s.allLogs[k] ^ sym_key(seed, 3 * N + 2 + k));
+    u64 sig[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+      u32 sc = fget<TB>(s.term, i);
+      sc |= fget<2>(s.st, i) << TB;
+      sc |= (g_voted(s, i) == N ? 1u : 0u) << (TB + 2);
+      sc |= fget<CIB>(s.commit, i) << (TB + 3);
+      sc |= (u32)popc32(row_bits(s.vresp, i)) << (TB + 3 + CIB);
+      sc |= (u32)popc32(row_bits(s.vgrant, i)) << (TB + 3 + CIB + 4);
+      sig[i] = ((u64)sc << 32) | (u64)s.log.v[i];
+    }
+    u32 lo = 0, hi = 0, rank_pi = 0;   // per server: the index range [lo, hi) of its signature class
+    bool distinct = true;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+      u32 l = 0, e = 0;
+#pragma unroll
+      for (int j = 0; j < N; ++j) { l += sig[j] < sig[i] ? 1u : 0u; e += sig[j] == sig[i] ? 1u : 0u; }
+      lo |= l << (4 * i); hi |= (l + e) << (4 * i);
+      rank_pi |= l << (3 * i);
+      distinct &= e == 1u;
+    }
+    u64 best = ~0ull;
+    if (distinct) {
+      best = sym_hash(s, rank_pi, seed);
+    } else {
+#pragma unroll 1
+      for (int p = 0; p < NPERM; ++p) {
+        const u32 pi = perm_of(p);
+        bool ok = true;
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+          const u32 x = (u32)pi_of(pi, i);
+          ok &= x >= ((lo >> (4 * i)) & 15u) && x < ((hi >> (4 * i)) & 15u);
+        }
+        if (ok) {
+          const u64 h = sym_hash(s, pi, seed);
+          best = h < best ? h : best;
+        }
+      }
+    }
+    const u64 fp = fmix64((best + base) ^ seed);
+    return fp ? fp : 1ull;
   }
 };
 

@@ -56,7 +56,7 @@ int main(int argc, char** argv) {
     else if (k == "-seed") o.seed = std::strtoull(val(), nullptr, 0);
     else if (k == "-no-inv-oom") o.tlc_compat_flags &= ~MC_COMPAT_INV_OUT_OF_MODEL;
     else if (k == "-no-disjunct-copies") o.tlc_compat_flags &= ~MC_COMPAT_DISJUNCT_COPIES;   // a disjunctive guard's successor counted once
-    else if (k == "-symmetry") {   // "tlc" (default): TLC's least-permuted-state rule; "orbit": the faster orbit mode
+    else if (k == "-symmetry") {   // "tlc" (default): TLC's least-permuted-state rule; "orbit": the faster orbit mode (tlc_membership; no effect for raft_original's SYMMETRY)
       const std::string v = val();
       if (v == "tlc") o.tlc_compat_flags |= MC_COMPAT_SYM_TLC;
       else if (v == "orbit") o.tlc_compat_flags &= ~MC_COMPAT_SYM_TLC;

@@ -325,6 +325,31 @@ std::string action_location(const std::string& module_path, const std::string& o
          std::to_string(c1) + " of module " + module_name(t);
 }
 
+std::string definition_text(const std::string& module_path, const std::string& op, int depth) {
+  std::string t;
+  try { t = read_text_file(module_path); } catch (const CfgError&) { return ""; }
+  size_t head = 0;
+  const size_t eq = definition_body(t, op, head);
+  if (eq == std::string::npos) {
+    if (depth >= 4) return "";
+    for (const auto& m : extends_of(t)) {
+      const std::string d = definition_text(dir_of(module_path) + "/" + m + ".tla", op, depth + 1);
+      if (!d.empty()) return d;
+    }
+    return "";
+  }
+  if (t.find('(', head) < eq && t.find('(', head) < t.find("==", head)) return "";   // op(params) == ...
+  size_t unit_end = t.size();
+  for (size_t nl = t.find('\n', head); nl != std::string::npos; nl = t.find('\n', nl + 1)) {
+    const size_t ls = nl + 1;
+    if (ls >= t.size()) break;
+    if (isalpha((unsigned char)t[ls]) || t.compare(ls, 4, "----") == 0 || t.compare(ls, 4, "====") == 0) { unit_end = ls; break; }
+  }
+  std::string out;
+  for (size_t p = skip_blank(t, eq); p < unit_end; p = skip_blank(t, p + 1)) out += t[p];
+  return out;
+}
+
 const std::vector<TVal>& trace_global(const TVal& v) {
   if (v.kind == TVal::Seq) return v.elems;
   if (v.kind == TVal::Rec) {

@@ -40,6 +40,10 @@ std::string find_trace_literal(const std::string& module_path, const std::string
 // then in the modules it EXTENDS (<dir>/<name>.tla, as TLC resolves them); "" if absent.
 std::string action_location(const std::string& module_path, const std::string& op, int depth = 0);
 
+// The body of `op == body` with blanks and comments removed, looked up like action_location; "" if
+// absent or if the definition takes parameters.
+std::string definition_text(const std::string& module_path, const std::string& op, int depth = 0);
+
 // The history sequence of a trace value: the value itself if it is a sequence, else its
 // `global` field (throws CfgError(MC_E_PARSE) otherwise).
 const std::vector<TVal>& trace_global(const TVal& v);

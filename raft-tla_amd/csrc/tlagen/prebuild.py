@@ -19,6 +19,8 @@ REF = os.environ.get("RAFTMC_REFERENCE", "/root/reference")
 
 SPECS = [(n, "configs/raft_original_mc.tla", "configs/%s.cfg" % n)
          for n in ("c1", "parity_single", "parity_pair", "parity_trio", "c2", "c2_noleader")]
+# C2 with SYMMETRY Permutations(Server) (TLC's rule): scripts/sym_bench.py checks the hand-compiled orbit count against it
+SPECS += [("c2_sym", "configs/raft_original_sym_mc.tla", "configs/c2_sym.cfg")]
 SPECS += [("toy_ring", "configs/tlagen/TokenRing.tla", "configs/tlagen/TokenRing.cfg"),
           ("toy_ring_full", "configs/tlagen/TokenRing.tla", "configs/tlagen/TokenRing_full.cfg"),
           ("countdown", "configs/tlagen/Countdown.tla", "configs/tlagen/Countdown.cfg"),

@@ -173,6 +173,8 @@ class ModelChecker:
     """One raftmc handle: mc_open on construction, mc_run in run()."""
 
     # sym_tlc: SYMMETRY as TLC applies it (the default, MC_COMPAT_SYM_TLC); False = the orbit mode
+    # (tlc_membership; raft_original's `SYMMETRY Name == Permutations(Server)` has no VIEW, so the
+    # two rules coincide there: one GPU, describe() shows "symmetry": true, "permutations": N!)
     # disjunct_copies: TLC's generated count of a disjunctive guard (MC_COMPAT_DISJUNCT_COPIES, default)
     def __init__(self, spec, config=None, workers=1, deadlock=True, device=0, max_depth=0,
                  fp_table_bytes=0, state_store_bytes=0, seed=0, inv_out_of_model=True, sym_tlc=True, disjunct_copies=True, n_gpus=1,
