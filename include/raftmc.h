@@ -213,28 +213,54 @@ int mc_action_location(const mc_ctx* ctx, const char* action, char** text, size_
  * report's estimate line. */
 int mc_collision_observed(mc_ctx* ctx, double* val);
 
-/* Checkpoint / recover (the two hand-compiled families and the generated path) — TLC's
- * `-checkpoint <minutes>` and `-recover <dir>`
- * (the states/ directory, reference .gitignore:3).  mc_set_checkpoint: every `every_levels`
- * completed BFS levels mc_run writes the search state (stored states, parent pointers, level
- * position, TLC's counters, the model's identity) to `path` (atomically: path.tmp, rename);
- * NULL or 0 disables.  mc_set_recover: the next mc_run resumes from `path` instead of Init
- * (the seen-set is rebuilt on the GPU from the stored states); generated/distinct/depth/per-action
- * counts continue exactly; kernel timings cover the resumed part.  A checkpoint of another
- * model or of another backend (or of the other SYMMETRY mode, or — raft_original — of a search with
- * SYMMETRY for one without it and the reverse, or — raft_original and the generated
- * path — a -workers N checkpoint for a -workers 1 search: its kept parents are not TLC's; a
- * -workers 1 checkpoint does resume a -workers N search) is refused (MC_E_INVALID), a truncated or
- * unreadable file MC_E_IO.  fp_table_bytes and state_store_bytes may be larger on recovery than when
- * the file was written (the seen-set is rebuilt at this run's size): that is how a run that ended
- * as CAPACITY_OVERFLOW goes on from its last checkpoint, which an overflow never overwrites.
- * Hand-compiled families: completed levels that do not fit the device store are kept in host
- * memory on save and on recovery (host spill).  The generated path has no host spill: a file that
- * does not fit the configured store or table ends as CAPACITY_OVERFLOW ("state store full",
- * "seen-set full"); it identifies the model by the generated code's key and its variable and
- * action names, not by the module's path.  A -workers N search that finds an event searches the
- * model again in FIFO order from Init, with neither path.  Single-GPU runs only: the mc_shard_*
- * calls return MC_E_UNSUPPORTED on a handle with a checkpoint or recover path set. */
+/* Checkpoint / recover (the two hand-compiled families and the generated path) -- TLC's
+ * `-checkpoint <minutes>` and `-recover <dir>` (the states/ directory, reference .gitignore:3).
+ *
+ * mc_set_checkpoint: every `every_levels` completed BFS levels mc_run writes the search state
+ * (stored states, parent pointers, level position, TLC's counters, the model's identity) to `path`
+ * (atomically: path.tmp, rename); NULL or 0 disables.  An overflow never overwrites a checkpoint.
+ * mc_set_recover: the next mc_run resumes from `path` instead of Init (the seen-set is rebuilt on
+ * the GPU from the stored states); generated/distinct/depth/per-action counts continue exactly, with
+ * the checkpoint's fingerprint seed; kernel timings cover the resumed part.
+ *
+ * On disk.  One GPU: one file, `path`.  raft_original with mc_opts.n_gpus = W > 1: every rank writes
+ * its own store, parent pointers rank-tagged as they are, to `path`.g<G>.r<k> (G: the levels
+ * completed, k: the rank); once all W files are complete, rank 0 writes the manifest `path` (the
+ * model, W, G, the seed, the search's counters and level table, no states) and then removes the
+ * rank files of the manifest it replaced.  At any moment the manifest names W complete rank files.
+ *
+ * Which source recovers where (raft_original): a manifest with its rank files, or a single-GPU
+ * file of either search order, resumes a search on any n_gpus in 1..8, the writer's or another:
+ * every stored state is fingerprinted again, placed with its new owner and its parent pointer
+ * rewritten, on the GPU, level by level.  The resumed search's counts,
+ * levels, state set and counterexamples are those of an uninterrupted run.  A single-GPU file on
+ * a single-GPU handle takes the single-GPU path, unchanged.  A manifest resumes a single-GPU
+ * handle only with workers != 1: a multi-GPU search is a -workers N search.
+ *
+ * Refused (MC_E_INVALID): a checkpoint of another model or of another backend (or of the other
+ * SYMMETRY mode, or -- raft_original -- of a search with SYMMETRY for one without it and the
+ * reverse, or -- raft_original and the generated path -- a -workers N checkpoint for a -workers 1
+ * single-GPU search: its kept parents are not TLC's; a -workers 1 checkpoint does resume a
+ * -workers N search); a manifest whose rank file is missing, is of another generation, world, rank
+ * or model, or whose level table disagrees with it; a parent pointer that names no state of the
+ * level before.  A truncated or unreadable file is MC_E_IO.
+ *
+ * Capacity.  fp_table_bytes and state_store_bytes may be larger on recovery than when the file was
+ * written, and n_gpus may be: that is how a run that ended as CAPACITY_OVERFLOW goes on from its
+ * last checkpoint, with a larger store or on more GPUs.  Hand-compiled families, one GPU, a
+ * single-GPU file: completed levels that do not fit the device store are kept in host memory on
+ * save and on recovery (host spill).  The multi-GPU search has no host spill, nor has a recovery
+ * from a manifest or at another GPU count: a rank whose share does not fit its store or seen-set
+ * ends the run as CAPACITY_OVERFLOW ("state store full") before the first level.  The generated
+ * path has no host spill either ("state store full", "seen-set full"); it identifies the model by
+ * the generated code's key and its variable and action names, not by the module's path.  A
+ * -workers N search that finds an event searches the model again in FIFO order from Init, with
+ * neither path.
+ *
+ * Still MC_E_UNSUPPORTED on a handle with either path set: every mc_shard_* call,
+ * mc_shard_run_rccl and mc_shard_run_loopback; mc_run with n_gpus > 1 for tlc_membership (its
+ * checkpoints are single-GPU); simulation and continue mode; and mc_set_checkpoint with
+ * count_final_level. */
 int mc_set_checkpoint(mc_ctx* ctx, const char* path, int32_t every_levels);
 int mc_set_recover(mc_ctx* ctx, const char* path);
 

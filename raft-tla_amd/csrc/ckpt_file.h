@@ -157,4 +157,158 @@ int read_gen_body(Reader& in, const GenHead& h, uint64_t n_init, size_t chunk_by
   return 0;
 }
 
+// ---------------------------------------------------------------- multi-GPU checkpoints
+// A raft_original search on W > 1 GPUs writes, every time it checkpoints, one file per rank,
+// `path`.g<G>.r<k> (G, the generation: the levels completed), and then the manifest `path`.  Both
+// have the framing above around one header:
+//  - the manifest ("RAFTMCS1", rank -1, no body): the search's counters, total = distinct, the
+//    per-action counters and the (states, generated) of every level;
+//  - a rank file ("RAFTMCR1"): the same counters, total / level_begin / level_count of that rank's
+//    store, its level rows (states = the rank's states of the level, generated = the level's states
+//    over all ranks, which must be the manifest's), then the rank's stored states and their parent
+//    pointers (rank-tagged ids) as a single-GPU file holds them.
+struct ShardHead {
+  char magic[8];
+  uint64_t nwp, total, level_begin, level_count, seed;
+  int64_t generated, distinct, depth, generated_in_model, n_act, n_levels, desc_len;
+  int64_t fifo;                       // 0: the sharded search is a -workers N search
+  int64_t rank, world, generation;
+};
+static_assert(sizeof(ShardHead) == 136, "the multi-GPU checkpoint headers are 136 bytes on disk");
+constexpr const char* kManifestMagic = "RAFTMCS1";
+constexpr const char* kRankMagic = "RAFTMCR1";
+constexpr const char* kOrigMagic = "RAFTMCK2";
+
+struct LevelRow { int64_t states = 0, generated = 0; };
+
+inline std::string rank_path(const std::string& path, int64_t generation, int rank) {
+  return path + ".g" + std::to_string(generation) + ".r" + std::to_string(rank);
+}
+
+// the first 8 bytes of `path` ("" when it has fewer or cannot be read)
+inline std::string file_magic(const std::string& path) {
+  const File f = open_file(path, "rb");
+  char m[8];
+  return f && std::fread(m, 1, 8, f.get()) == 8 ? std::string(m, 8) : std::string();
+}
+
+// the rank files of the manifest at `path` (if it is one) that a manifest of `generation` and
+// `world` does not name: what the writer removes once the new manifest is in place
+inline void remove_stale_rank_files(const std::string& path, int64_t old_generation, int64_t old_world, int64_t generation, int64_t world) {
+  for (int64_t k = 0; k < old_world && k < 8; ++k)
+    if (old_generation != generation || k >= world) (void)std::remove(rank_path(path, old_generation, (int)k).c_str());
+}
+
+// What a recovery reads (orig_reshard.hip): W parts, each a file that holds, from `body` on, the
+// `total` states of one source rank and then their parent pointers, level after level
+// (level_count[L] of them in level L).  A single-GPU file is one part with untagged ids.
+struct SourcePart {
+  std::string path;
+  uint64_t body = 0, total = 0;
+  std::vector<uint64_t> level_count;
+};
+struct ShardSource {
+  int world = 0;
+  bool sharded = false;               // a manifest (ids carry their rank) / a single-GPU file
+  uint64_t seed = 0;
+  int64_t fifo = 0, generated = 0, distinct = 0, depth = 0, generated_in_model = 0, generation = 0;
+  std::vector<int64_t> act_generated, act_distinct;
+  std::vector<LevelRow> levels;       // of the whole search
+  std::vector<SourcePart> parts;
+};
+
+// the bytes behind the read position, which stays where it was
+inline bool bytes_left(FILE* f, uint64_t& n) {
+  const long at = std::ftell(f);
+  if (at < 0 || std::fseek(f, 0, SEEK_END) != 0) return false;
+  const long end = std::ftell(f);
+  if (end < at || std::fseek(f, at, SEEK_SET) != 0) return false;
+  n = (uint64_t)(end - at);
+  return true;
+}
+
+// Opens the source at `path` for a model of nwp words, n_act actions and description desc: a
+// manifest with its rank files, or a single-GPU raft_original file.  Everything a recovery later
+// indexes with is checked here, on the host: the level tables against the totals, the rank files
+// against the manifest (generation, world, rank, seed, levels) and each file's length.  A missing rank
+// file, one of another generation, world, rank or model, and tables that disagree are
+// MC_E_INVALID; a file shorter than its header says is MC_E_IO.
+inline int open_source(const std::string& path, uint64_t nwp, int64_t n_act, const std::string& desc, ShardSource& s, std::string& err) {
+  s = ShardSource();
+  const uint64_t slot = nwp * 4 + 8;
+  const std::string magic = file_magic(path);
+  if (magic != kManifestMagic) {   // a single-GPU file (or nothing Reader::head accepts)
+    OrigHead h;
+    Reader in(path);
+    if (int rc = in.head(kOrigMagic, nwp, n_act, desc, h, s.act_generated, s.act_distinct, s.levels, err)) return rc;
+    uint64_t in_levels = 0, left = 0;
+    SourcePart p;
+    for (const auto& lv : s.levels) {
+      if (lv.states <= 0 || (uint64_t)lv.states > h.total) return in.other_model(err);
+      in_levels += (uint64_t)lv.states;
+      p.level_count.push_back((uint64_t)lv.states);
+    }
+    if (h.total == 0 || h.total > (1ull << 37) || in_levels != h.total || h.level_count != (uint64_t)s.levels.back().states ||
+        h.level_begin != h.total - h.level_count || h.depth != h.n_levels || h.distinct != (int64_t)h.total || (h.fifo != 0 && h.fifo != 1))
+      return in.other_model(err);
+    if (!bytes_left(in.file(), left) || left < h.total * slot) return in.truncated(err);
+    if (left > h.total * slot) return in.other_model(err);
+    p.path = path; p.body = (uint64_t)std::ftell(in.file()); p.total = h.total;
+    s.parts.push_back(p);
+    s.world = 1; s.sharded = false; s.seed = h.seed; s.fifo = h.fifo; s.generated = h.generated; s.distinct = h.distinct;
+    s.depth = h.depth; s.generated_in_model = h.generated_in_model; s.generation = h.depth;
+    return 0;
+  }
+  ShardHead m;
+  {
+    Reader in(path);
+    if (int rc = in.head(kManifestMagic, nwp, n_act, desc, m, s.act_generated, s.act_distinct, s.levels, err)) return rc;
+    uint64_t in_levels = 0, left = 0;
+    for (const auto& lv : s.levels) {
+      if (lv.states <= 0 || (uint64_t)lv.states > m.total) return in.other_model(err);
+      in_levels += (uint64_t)lv.states;
+    }
+    if (m.world < 1 || m.world > 8 || m.rank != -1 || m.fifo != 0 || m.total == 0 || m.total >= (1ull << 40) || in_levels != m.total ||
+        m.level_count != (uint64_t)s.levels.back().states || m.level_begin != m.total - m.level_count || m.depth != m.n_levels ||
+        m.generation != m.depth || m.distinct != (int64_t)m.total)
+      return in.other_model(err);
+    if (!bytes_left(in.file(), left)) return in.truncated(err);
+    if (left != 0) return in.other_model(err);
+  }
+  std::vector<uint64_t> level_sum(s.levels.size(), 0);
+  for (int k = 0; k < (int)m.world; ++k) {
+    SourcePart p;
+    p.path = rank_path(path, m.generation, k);
+    Reader in(p.path);
+    if (!in.file()) { err = "checkpoint " + path + ": rank file " + p.path + " is missing"; return MC_E_INVALID; }
+    ShardHead h;
+    std::vector<int64_t> ag, ad;
+    std::vector<LevelRow> rows;
+    if (int rc = in.head(kRankMagic, nwp, n_act, desc, h, ag, ad, rows, err)) return rc;
+    if (h.rank != k || h.world != m.world || h.generation != m.generation || h.seed != m.seed || h.n_levels != m.n_levels ||
+        h.total > (1ull << 37))
+      return in.other_model(err);
+    uint64_t mine = 0, left = 0;
+    for (size_t l = 0; l < rows.size(); ++l) {
+      if (rows[l].generated != s.levels[l].states || rows[l].states < 0 || rows[l].states > s.levels[l].states) return in.other_model(err);
+      mine += (uint64_t)rows[l].states;
+      level_sum[l] += (uint64_t)rows[l].states;
+      p.level_count.push_back((uint64_t)rows[l].states);
+    }
+    if (mine != h.total || h.level_count != p.level_count.back() || h.level_begin != h.total - h.level_count) return in.other_model(err);
+    if (!bytes_left(in.file(), left) || left < h.total * slot) return in.truncated(err);
+    if (left > h.total * slot) return in.other_model(err);
+    p.body = (uint64_t)std::ftell(in.file()); p.total = h.total;
+    s.parts.push_back(p);
+  }
+  for (size_t l = 0; l < s.levels.size(); ++l)
+    if (level_sum[l] != (uint64_t)s.levels[l].states) {
+      err = "checkpoint " + path + ": the rank files' level tables disagree with the manifest";
+      return MC_E_INVALID;
+    }
+  s.world = (int)m.world; s.sharded = true; s.seed = m.seed; s.fifo = 0; s.generated = m.generated; s.distinct = m.distinct;
+  s.depth = m.depth; s.generated_in_model = m.generated_in_model; s.generation = m.generation;
+  return 0;
+}
+
 }  // namespace rmc::ckpt

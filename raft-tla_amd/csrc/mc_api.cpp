@@ -258,8 +258,10 @@ namespace {
 int run_multi(mc_ctx* c) {
   const int W = c->n_gpus;
   std::string err;
-  if (!c->ro.checkpoint_path.empty() || !c->ro.recover_path.empty()) {
-    c->last_error = "checkpoint/recover apply to single-GPU runs (n_gpus = 1)";
+  // checkpoint / recover on n_gpus > 1 exist for raft_original; another family
+  // refuses rather than silently writing no checkpoint or starting from Init
+  if ((!c->ro.checkpoint_path.empty() || !c->ro.recover_path.empty()) && c->be->family() != "raft_original") {
+    c->last_error = "checkpoint/recover with n_gpus > 1 exist for raft_original only: " + c->be->family() + " checkpoints single-GPU runs (n_gpus = 1)";
     return MC_E_UNSUPPORTED;
   }
   int ndev = 0;
@@ -558,13 +560,14 @@ int mc_exit_code(const mc_ctx* c) {
 }
 
 // ------------------------------------------------------------------ sharded BFS
-// checkpoint / recover apply to single-GPU runs only: a sharded run refuses them rather than
-// silently writing no checkpoint or starting from Init
+// checkpoint / recover belong to mc_run (one GPU, or raft_original with mc_opts.n_gpus > 1): the
+// step API and the caller-driven sharded loops refuse them rather than silently writing no
+// checkpoint or starting from Init
 #define SHARD_GUARD() \
   if (!c) return MC_E_INVALID; \
   if (!c->be) return MC_E_STATE; \
   if (!c->ro.checkpoint_path.empty() || !c->ro.recover_path.empty()) { \
-    c->last_error = "checkpoint/recover apply to single-GPU runs (mc_run); a sharded run cannot use them"; \
+    c->last_error = "checkpoint/recover apply to mc_run (single-GPU runs, and raft_original with n_gpus > 1); the mc_shard_* calls cannot use them"; \
     return MC_E_UNSUPPORTED; \
   } \
   if (c->ro.sim_walks > 0) { \
@@ -717,7 +720,7 @@ int mc_shard_run_loopback(mc_ctx* const* ctxs, int32_t world) {
     if (!ctxs[r] || !ctxs[r]->be) return MC_E_INVALID;
     for (int q = 0; q < r; ++q) if (ctxs[q] == ctxs[r]) return MC_E_INVALID;
     if (!ctxs[r]->ro.checkpoint_path.empty() || !ctxs[r]->ro.recover_path.empty()) {
-      ctxs[r]->last_error = "checkpoint/recover apply to single-GPU runs (mc_run); a sharded run cannot use them";
+      ctxs[r]->last_error = "checkpoint/recover apply to mc_run (single-GPU runs, and raft_original with n_gpus > 1); the mc_shard_* calls cannot use them";
       return MC_E_UNSUPPORTED;
     }
     if (ctxs[r]->ro.sim_walks > 0) {

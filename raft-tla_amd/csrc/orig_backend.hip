@@ -59,6 +59,7 @@
 #include "orig_spec.h"
 #include "orig_text.h"
 #include "rccl_api.h"
+#include "reshard_plan.h"
 #include "shard_transport.h"
 #include "sim_rng.h"
 #include "state_store.h"
@@ -1386,6 +1387,7 @@ __global__ void __launch_bounds__(BS) orig_reinsert(const u32* states, u64 n, u6
 
 #include "orig_sim.hip"   // simulation mode: the walker kernel and the host replay of one walk
 #include "orig_sym.hip"   // SYMMETRY Permutations(Server): the orbit-fingerprint generate and reinsert kernels
+#include "orig_reshard.hip"   // recovery at another GPU count: the classify / scan / place kernels
 
 }  // namespace rmc
 #include "dev_owner.h"   // host only, included here so that the device code above keeps its text
@@ -1972,7 +1974,7 @@ class OrigGpu : public Backend {
   // Level 0: the checkpoint's frontier (TLC -recover), or Init (raft_original.tla:139-159), one
   // state, generated and distinct.  ended: Init is outside the model or violates an invariant.
   int init_level0(const RunOpts& o, Search& s, RunResult& r, bool& ended, std::string& err) {
-    if (!o.recover_path.empty()) return load_checkpoint(o.recover_path, s.fifo, r, s.level_begin, s.level_count, err);
+    if (!o.recover_path.empty()) return load_checkpoint(o.recover_path, s.fifo, s, r, s.level_begin, s.level_count, ended, err);
     W s0; S::init(s0);
     u32 w0[S::NW]; S::pack(s0, w0);
     InitWords<NWP> wp = {}; for (int q = 0; q < S::NW; ++q) wp.w[q] = w0[q];
@@ -2330,8 +2332,226 @@ class OrigGpu : public Backend {
     ckpt_of_run(r, desc, h);
     return ckpt::write_file(path, h, desc, r.act_generated, r.act_distinct, r.levels, [&](FILE* f) { return store_.write_body(f); }, err);
   }
-  int load_checkpoint(const std::string& path, bool fifo, RunResult& r, u64& level_begin, u64& level_count, std::string& err) {
+  // the rank files of a multi-GPU search (ckpt_file.h): this rank's store as it is,
+  // parent pointers rank-tagged; levels: this rank's states of every level of sres_
+  int save_rank_file(const std::string& path, std::string& err) {
+    const std::string desc = describe_json();
+    ckpt::ShardHead h;
+    std::memset(&h, 0, sizeof h);
+    std::memcpy(h.magic, ckpt::kRankMagic, 8);
+    h.nwp = NWP; h.total = store_.total(); h.level_begin = sh_level_begin_; h.level_count = sh_level_count_;
+    h.rank = rank_; h.world = world_; h.generation = sres_.depth;
+    ckpt_of_run(sres_, desc, h);
+    std::vector<ckpt::LevelRow> rows(sres_.levels.size());
+    if (sh_levels_.size() != rows.size()) { err = "checkpoint: this rank's level table is incomplete"; return MC_E_STATE; }
+    for (size_t l = 0; l < rows.size(); ++l) rows[l] = {(int64_t)sh_levels_[l], sres_.levels[l].states};
+    return ckpt::write_file(ckpt::rank_path(path, h.generation, rank_), h, desc, sres_.act_generated, sres_.act_distinct, rows,
+                            [&](FILE* f) { return store_.write_body(f); }, err);
+  }
+  // ... and, by rank 0 once every rank file is complete, the manifest; the rank files it replaces go last
+  int save_manifest(const std::string& path, std::string& err) {
+    const std::string desc = describe_json();
+    ckpt::ShardHead h, old;
+    std::memset(&h, 0, sizeof h);
+    std::memset(&old, 0, sizeof old);
+    std::memcpy(h.magic, ckpt::kManifestMagic, 8);
+    h.nwp = NWP; h.total = (u64)sres_.distinct; h.level_count = (u64)sres_.levels.back().states; h.level_begin = h.total - h.level_count;
+    h.rank = -1; h.world = world_; h.generation = sres_.depth;
+    ckpt_of_run(sres_, desc, h);
+    {   // the manifest this one replaces names the rank files to remove
+      const ckpt::File f = ckpt::open_file(path, "rb");
+      if (!f || std::fread(&old, sizeof old, 1, f.get()) != 1 || std::memcmp(old.magic, ckpt::kManifestMagic, 8) != 0) old.world = 0;
+    }
+    if (int rc = ckpt::write_file(path, h, desc, sres_.act_generated, sres_.act_distinct, sres_.levels, [](FILE*) { return true; }, err)) return rc;
+    ckpt::remove_stale_rank_files(path, old.generation, old.world, h.generation, h.world);
+    return 0;
+  }
+
+  // ---------------------------------------------------------------- recovery at any GPU count
+  // (orig_reshard.hip)  What rank `me` of `world` holds once the source is in its store:
+  struct Resharded {
+    std::vector<u64> local;   // its states of every level
+    u64 total = 0;            // ... of all levels
+    bool overflow = false;    // its share does not fit its store (nothing was written behind the end)
+  };
+  // Reads the whole source level by level in the canonical order, in blocks through one pinned
+  // bounce buffer, and places this rank's share in store_ (states from slot 0, levels one behind the
+  // other).  Kernel times go to sres_.kernels[k0] (classify) and [k0 + 1] (place).  The seen-set is
+  // not touched.  A parent pointer that names no state of the level before: MC_E_INVALID.
+  int reshard_load(const ckpt::ShardSource& src, int me, int world, int k0, Resharded& out, std::string& err) {
+    const int SW = src.world;
+    const size_t nl = src.levels.size();
+    u64 max_level = 0, max_slice = 0;
+    for (size_t l = 0; l < nl; ++l) {
+      max_level = std::max<u64>(max_level, (u64)src.levels[l].states);
+      for (int r = 0; r < SW; ++r) max_slice = std::max<u64>(max_slice, src.parts[r].level_count[l]);
+    }
+    const u64 block = std::min<u64>(StateStore::kBlock, max_slice), nwg_max = (block + BS - 1) / BS;
+    struct Tmp {   // freed on every way out
+      u32* st = nullptr; u64* me = nullptr; unsigned char* own = nullptr; u32* cnt = nullptr; u64* off = nullptr;
+      u64* map0 = nullptr; u64* map1 = nullptr; u64* run = nullptr;
+      u32* h_st = nullptr; u64* h_me = nullptr;
+      DevOwner<HipDevApi> res;
+    } t;
+    HIPCHK(t.res.device(&t.st, block * NWP * 4));
+    HIPCHK(t.res.device(&t.me, block * 8));
+    HIPCHK(t.res.device(&t.own, block));
+    HIPCHK(t.res.device(&t.cnt, nwg_max * RESHARD_MAX_WORLD * 4));
+    HIPCHK(t.res.device(&t.off, nwg_max * RESHARD_MAX_WORLD * 8));
+    HIPCHK(t.res.device(&t.map0, max_level * 8));
+    HIPCHK(t.res.device(&t.map1, max_level * 8));
+    HIPCHK(t.res.device(&t.run, (RESHARD_MAX_WORLD + 1) * 8));
+    HIPCHK(t.res.pinned(&t.h_st, block * NWP * 4));
+    HIPCHK(t.res.pinned(&t.h_me, block * 8));
+    // two read positions per part: its states and its parent pointers, both in level order
+    std::vector<ckpt::File> fs, fm;
+    for (int r = 0; r < SW; ++r) {
+      const ckpt::SourcePart& p = src.parts[r];
+      fs.push_back(ckpt::open_file(p.path, "rb"));
+      fm.push_back(ckpt::open_file(p.path, "rb"));
+      if (!fs[r] || !fm[r] || std::fseek(fs[r].get(), (long)p.body, SEEK_SET) != 0 ||
+          std::fseek(fm[r].get(), (long)(p.body + p.total * NWP * 4), SEEK_SET) != 0) {
+        err = "cannot read checkpoint " + p.path;
+        return MC_E_IO;
+      }
+    }
+    HIPCHK(hipMemsetAsync(d_ctr_ + K_ERR, 0, 8, stream_));
+    ReshardPlaceArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.me = (u32)me; a.states = store_.states(); a.meta = store_.meta(); a.cap = store_.cap(); a.ctr = (unsigned long long*)d_ctr_;
+    a.in_states = t.st; a.in_meta = t.me; a.owner = t.own; a.wg_off = t.off;
+    a.map_prev = t.map1; a.map_cur = t.map0;
+    ReshardLevel cur;
+    std::memset(&cur, 0, sizeof cur);
+    double read_s = 0;
+    out = Resharded();
+    for (size_t l = 0; l < nl; ++l) {
+      cur.world = (u32)SW;
+      for (int r = 0; r < SW; ++r) { cur.begin[r] += l ? src.parts[r].level_count[l - 1] : 0; cur.count[r] = src.parts[r].level_count[l]; }
+      a.level_size = reshard_canonical(cur);
+      HIPCHK(hipMemsetAsync(t.run, 0, RESHARD_MAX_WORLD * 8, stream_));
+      a.pos0 = 0;
+      for (int r = 0; r < SW; ++r) {
+        for (u64 b = 0; b < cur.count[r]; b += block) {
+          const u64 n = std::min<u64>(block, cur.count[r] - b);
+          const auto tr = std::chrono::steady_clock::now();
+          if (std::fread(t.h_st, 4, n * NWP, fs[r].get()) != n * NWP || std::fread(t.h_me, 8, n, fm[r].get()) != n) {
+            err = "checkpoint " + src.parts[r].path + " is truncated";
+            return MC_E_IO;
+          }
+          read_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - tr).count();
+          HIPCHK(hipMemcpyAsync(t.st, t.h_st, n * NWP * 4, hipMemcpyHostToDevice, stream_));
+          HIPCHK(hipMemcpyAsync(t.me, t.h_me, n * 8, hipMemcpyHostToDevice, stream_));
+          const unsigned nwg = (unsigned)((n + BS - 1) / BS);
+          a.n = n;
+          if (int rc = timed(k0, [&] {
+                hipLaunchKernelGGL((orig_reshard_classify<S>), dim3(nwg), dim3(BS), 0, stream_, (const u32*)t.st, n, (u64)src.seed, (u32)world, t.own, t.cnt);
+                hipLaunchKernelGGL(orig_reshard_scan, dim3(1), dim3(BS), 0, stream_, (const u32*)t.cnt, (u32)nwg, t.run, t.off);
+              }, err)) return rc;
+          if (int rc = timed(k0 + 1, [&] { hipLaunchKernelGGL((orig_reshard_place<NWP>), dim3(nwg), dim3(BS), 0, stream_, a); }, err)) return rc;
+          HIPCHK(hipStreamSynchronize(stream_));   // the bounce buffer is free again
+          harvest();
+          sres_.kernels[k0].algo_bytes += (double)n * (NWP * 4 + 1);
+          sres_.kernels[k0 + 1].algo_bytes += (double)n * (8 + 1 + 8) + (double)n / world * (2.0 * NWP * 4 + 8);
+          a.pos0 += n;
+        }
+      }
+      u64 h[RESHARD_MAX_WORLD + 1];   // the level's states per owner, and the error word
+      HIPCHK(hipMemcpyAsync(t.run + RESHARD_MAX_WORLD, d_ctr_ + K_ERR, 8, hipMemcpyDeviceToDevice, stream_));
+      HIPCHK(hipMemcpyAsync(h, t.run, sizeof h, hipMemcpyDeviceToHost, stream_));
+      HIPCHK(hipStreamSynchronize(stream_));
+      u64 sum = 0;
+      for (int o = 0; o < RESHARD_MAX_WORLD; ++o) sum += h[o];
+      if ((h[RESHARD_MAX_WORLD] & OE_RESHARD_PARENT) || sum != a.level_size) {
+        err = "checkpoint " + src.parts[0].path + " is not a checkpoint of this model (a parent pointer of level " + std::to_string(l + 1) +
+              " names no state of the level before)";
+        return MC_E_INVALID;
+      }
+      out.local.push_back(h[me]);
+      out.total += h[me];
+      if (out.total > store_.cap()) { out.overflow = true; break; }
+      for (int o = 0; o < RESHARD_MAX_WORLD; ++o) a.owner_begin[o] += h[o];
+      a.prev = cur; a.prev_size = a.level_size;
+      u64* const done_map = a.map_cur;
+      a.map_cur = const_cast<u64*>(a.map_prev); a.map_prev = done_map;
+    }
+    HIPCHK(hipMemsetAsync(d_ctr_ + K_ERR, 0, 8, stream_));
+    HIPCHK(hipStreamSynchronize(stream_));
+    if (progress_)
+      std::fprintf(stderr, "recover: rank %d of %d read %zu levels of %d part(s): file read %.3f s, classify %.3f ms, place %.3f ms\n", me, world, nl,
+                   SW, read_s, sres_.kernels[k0].ms, sres_.kernels[k0 + 1].ms);
+    return 0;
+  }
+  // the seen-set of a -workers N search (8-B entries) from this rank's n stored states; full: the table is
+  int reshard_reinsert(u64 n, u64 seed, int k, bool& full, std::string& err) {
+    full = false;
+    if (n) {
+      if (int rc = timed(k, [&] {
+            hipLaunchKernelGGL((orig_reinsert<S, 1>), dim3((unsigned)((n + BS - 1) / BS)), dim3(BS), 0, stream_, (const u32*)store_.states(), n, d_table_,
+                               2 * table_mask_ + 1, seed, (unsigned long long*)d_ctr_);
+          }, err)) return rc;
+      sres_.kernels[k].algo_bytes += (double)n * (NWP * 4 + 8);
+    }
+    u64 e = 0;
+    HIPCHK(hipMemcpyAsync(&e, d_ctr_ + K_ERR, 8, hipMemcpyDeviceToHost, stream_));
+    HIPCHK(hipStreamSynchronize(stream_));
+    harvest();
+    full = e != 0;
+    HIPCHK(hipMemsetAsync(d_ctr_ + K_ERR, 0, 8, stream_));
+    return 0;
+  }
+  static void run_of_source(const ckpt::ShardSource& src, RunResult& r) {
+    r.seed = src.seed; r.generated = src.generated; r.distinct = src.distinct; r.depth = src.depth; r.generated_in_model = src.generated_in_model;
+    r.act_generated = src.act_generated; r.act_distinct = src.act_distinct;
+    r.levels.clear();
+    for (const auto& lv : src.levels) r.levels.push_back({lv.states, lv.generated, 0.0});
+  }
+  // the text of a recovery whose share did not fit: r holds the source's counters
+  static std::string reshard_full_error(const RunResult& r, int world, u64 cap) {
+    return "state store full (raise state_store_bytes or recover on more GPUs): the checkpoint's " + std::to_string(r.distinct) +
+           " states do not fit " + std::to_string(world) + " store(s) of " + std::to_string(cap) +
+           " slots (a recovery from a multi-GPU checkpoint or at another GPU count does not spill to the host); the summary counts the " +
+           std::to_string(r.distinct) + " states of the " + std::to_string(r.depth) + " completed levels;";
+  }
+
+  // mc_run on one GPU from a multi-GPU checkpoint: W' = 1 of the path above into the single-GPU store.
+  // ended: the file does not fit the device store (CAPACITY_OVERFLOW: this path has no host spill)
+  int load_resharded(const std::string& path, bool fifo, const Search& s, RunResult& r, u64& level_begin, u64& level_count, bool& ended,
+                     std::string& err) {
+    if (fifo) {
+      err = "checkpoint " + path + " was written by a multi-GPU search, a -workers N search: its kept parents are not TLC's single-worker "
+            "FIFO ones, so it cannot resume a -workers 1 search";
+      return MC_E_INVALID;
+    }
+    ckpt::ShardSource src;
+    if (int rc = ckpt::open_source(path, NWP, OA_NACT, describe_json(), src, err)) return rc;
+    sres_ = new_result(src.seed, {"orig_reshard_classify", "orig_reshard_place", "orig_reinsert"});
+    pending_.clear();
+    Resharded got;
+    if ((u64)src.distinct <= store_.cap())
+      if (int rc = reshard_load(src, 0, 1, 0, got, err)) return rc;
+    run_of_source(src, r);
+    if ((u64)src.distinct > store_.cap() || got.overflow) {
+      r.verdict = MC_VERDICT_CAPACITY_OVERFLOW;
+      r.error = reshard_full_error(r, 1, store_.cap());
+      store_.set_total(0);
+      finish(r, s.t0);
+      ended = true;
+      return 0;
+    }
+    bool full = false;
+    if (int rc = reshard_reinsert(got.total, src.seed, 2, full, err)) return rc;
+    if (full) { err = "fingerprint table too small for the checkpoint (raise fp_table_bytes)"; return MC_E_OOM; }
+    for (const auto& k : sres_.kernels) r.kernels.push_back(k);
+    store_.set_total(got.total);
+    level_count = got.local.back(); level_begin = got.total - level_count;
+    return 0;
+  }
+
+  int load_checkpoint(const std::string& path, bool fifo, const Search& s, RunResult& r, u64& level_begin, u64& level_count, bool& ended,
+                      std::string& err) {
     HIPCHK(hipMemsetAsync(d_ctr_, 0, K_NCTR * 8, stream_));
+    if (ckpt::file_magic(path) == ckpt::kManifestMagic) return load_resharded(path, fifo, s, r, level_begin, level_count, ended, err);
     ckpt::OrigHead h;
     ckpt::Reader in(path);
     if (int rc = in.head("RAFTMCK2", NWP, OA_NACT, describe_json(), h, r.act_generated, r.act_distinct, r.levels, err)) return rc;
@@ -2386,13 +2606,15 @@ class OrigGpu : public Backend {
     const u64 fp0 = fp64(w0, sres_.seed);
     store_.set_total(0); sh_level_begin_ = 0; sh_level_count_ = 0; sh_new_ = 0;
     store_.reset();
-    if ((int)fp_owner(fp0, (u32)world) == rank) {
+    sh_levels_.assign(1, 0);
+    // (a recovering search takes its first levels from the checkpoint: shard_run_native, shard_recover)
+    if (o.recover_path.empty() && (int)fp_owner(fp0, (u32)world) == rank) {
       u32 wp[NWP] = {0}; for (int q = 0; q < S::NW; ++q) wp[q] = w0[q];
       HIPCHK(hipMemcpy(d_table_ + (fp0 & sh_table_mask()), &fp0, 8, hipMemcpyHostToDevice));
       HIPCHK(hipMemcpy(store_.states(), wp, NWP * 4, hipMemcpyHostToDevice));
       const u64 nometa = ~0ull;
       HIPCHK(hipMemcpy(store_.meta(), &nometa, 8, hipMemcpyHostToDevice));
-      store_.set_total(1); sh_level_count_ = 1;
+      store_.set_total(1); sh_level_count_ = 1; sh_levels_[0] = 1;
     }
     sres_.generated = 1; sres_.distinct = 1; sres_.depth = 1;
     sres_.levels.push_back({1, 0, 0.0});
@@ -2517,7 +2739,7 @@ class OrigGpu : public Backend {
                      std::to_string(sres_.depth) + " completed levels";
     } else {
       sres_.distinct += g[0];
-      if (g[0] > 0) { sres_.levels.push_back({g[0], 0, 0.0}); sres_.depth += 1; }
+      if (g[0] > 0) { sres_.levels.push_back({g[0], 0, 0.0}); sres_.depth += 1; sh_levels_.push_back(sh_new_); }
     }
     if (!*done && g[4]) { sres_.verdict = MC_VERDICT_INVARIANT_VIOLATION; *done = 1; sres_.left_on_queue = g[0]; }
     if (!*done && sopts_.check_deadlock && g[5]) { sres_.verdict = MC_VERDICT_DEADLOCK; *done = 1; sres_.left_on_queue = g[0]; }
@@ -2556,6 +2778,7 @@ class OrigGpu : public Backend {
 
   int shard_read_state(uint64_t gid, std::string& text, uint64_t* meta, std::string& err) const override {
     const u64 local = gid & ((1ull << 37) - 1);
+    if (!store_.states()) { err = "shard_read_state: the device memory of this handle was released"; return MC_E_STATE; }
     if (local >= store_.total()) { err = "shard_read_state: state id outside this rank's store"; return MC_E_INVALID; }
     u32 w[NWP]; u64 m = 0;
     if (!store_.read(local, w, &m)) { err = "readback failed"; return MC_E_NO_DEVICE; }
@@ -2637,10 +2860,43 @@ class OrigGpu : public Backend {
     const u64 chunk = chunk_states_;
     auto rounds = [&](u64 n) -> int64_t { return (int64_t)((n + chunk - 1) / chunk); };
     int64_t nchunks = 0;
+    int64_t start_flags = 0;   // a recovered share that does not fit this rank's store or seen-set
+    if (!sopts_.recover_path.empty())
+      if (int rc = shard_recover(start_flags, err)) return rc;
     {   // agree on the first level's chunk rounds (only the owner of Init holds a state)
       int64_t z[MC_SHARD_NSTAT] = {0};
+      z[3] = start_flags;
       if (int rc = allreduce_level(z, rounds(sh_level_count_), nchunks)) return rc;
+      start_flags = z[3];
     }
+    if (start_flags || (!sopts_.recover_path.empty() && sopts_.max_depth && sres_.depth >= sopts_.max_depth)) {
+      // the recovered search ends before its first level: some rank's share did not fit, or the
+      // checkpoint already is as deep as this run may go
+      if (start_flags) {
+        sres_.verdict = MC_VERDICT_CAPACITY_OVERFLOW;
+        std::ostringstream os; os << "error flags 0x" << std::hex << start_flags << " raised on some rank while recovering: ";
+        sres_.error = os.str() + ((start_flags & OE_CAP_STORE) ? reshard_full_error(sres_, world_, store_.cap()) : std::string("fingerprint table full (raise fp_table_bytes);"));
+      } else {
+        sres_.verdict = MC_VERDICT_DEPTH_LIMIT;
+        sres_.left_on_queue = sres_.levels.back().states;
+      }
+      sviol_act_.clear();
+      finish(sres_, st0_);
+      return 0;
+    }
+    // TLC -checkpoint on W GPUs: every rank its own file, then, once all of them are
+    // complete, rank 0 the manifest; a rank that could not write stops every rank
+    auto checkpoint = [&]() -> int {
+      std::string werr;
+      int wrc = save_rank_file(sopts_.checkpoint_path, werr);
+      int64_t z[MC_SHARD_NSTAT] = {0}, unused = 0;
+      z[3] = wrc ? 1 : 0;
+      if (int rc = allreduce_level(z, 0, unused)) return rc;
+      if (!z[3] && me == 0) wrc = save_manifest(sopts_.checkpoint_path, werr);
+      if (z[3] && !wrc) { wrc = MC_E_IO; werr = "writing checkpoint " + sopts_.checkpoint_path + " failed on another rank"; }
+      if (wrc) err = werr;
+      return wrc;
+    };
     const u64 route_cap = chunk_states_ * S::NI;
     // count_final_level: the level at depth max_depth is never expanded, so its new states are
     // deduplicated by their owners, counted and invariant-checked by the generating rank, but
@@ -2757,9 +3013,36 @@ class OrigGpu : public Backend {
       if (last) unstored_ = sh_new_;   // this rank's share of the final level: counted, not in the store
       int done = 0;
       if (int rc = shard_level_commit(g, &done, err)) return rc;
+      // as on one GPU: behind every checkpoint_every-th completed level that left a frontier, the
+      // level a depth limit stops at included; never behind a level that ended in an error
+      if (sopts_.checkpoint_every > 0 && !sopts_.checkpoint_path.empty() && (!done || sres_.verdict == MC_VERDICT_DEPTH_LIMIT) &&
+          g[0] > 0 && sres_.depth % sopts_.checkpoint_every == 0)
+        if (int rc = checkpoint()) return rc;
       if (done) break;
       nchunks = next_chunks;
     }
+    return 0;
+  }
+
+  // TLC -recover on W' GPUs: this rank's share of the source (a multi-GPU checkpoint of any world
+  // size, or a single-GPU file of either search order) into its store, its seen-set rebuilt, the
+  // search's counters the source's.  flags: OE_CAP_STORE / OE_TABLE_FULL when the share does not fit.
+  int shard_recover(int64_t& flags, std::string& err) {
+    ckpt::ShardSource src;
+    if (int rc = ckpt::open_source(sopts_.recover_path, NWP, OA_NACT, describe_json(), src, err)) return rc;
+    const int k0 = (int)sres_.kernels.size();
+    for (const char* k : {"orig_reshard_classify", "orig_reshard_place", "orig_reinsert"}) sres_.kernels.push_back({k, 0, 0, 0});
+    Resharded got;
+    if (int rc = reshard_load(src, rank_, world_, k0, got, err)) return rc;
+    run_of_source(src, sres_);
+    sh_levels_ = got.local;
+    if (got.overflow) { flags |= OE_CAP_STORE; sh_levels_.resize(src.levels.size(), 0); got.total = 0; }
+    bool full = false;
+    if (int rc = reshard_reinsert(got.total, src.seed, k0 + 2, full, err)) return rc;
+    if (full) flags |= OE_TABLE_FULL;
+    store_.set_total(got.total);
+    sh_level_count_ = got.overflow ? 0 : got.local.back(); sh_level_begin_ = got.total - sh_level_count_;
+    sh_next_write_ = got.total; sh_new_ = 0;
     return 0;
   }
 
@@ -2795,6 +3078,7 @@ class OrigGpu : public Backend {
   u64 fill_counts_route_[8] = {0};
   u64 sviol_parent_ = 0; u32 sviol_bad_ = 0; std::string sviol_act_, sviol_text_;
   u64 sh_event_ = ~0ull;
+  std::vector<u64> sh_levels_;   // this rank's states of every level of sres_.levels (the rank file's level rows)
   bool last_fifo_ = true;   // seen-set layout of the last single-GPU run (16-B keyed / 8-B entries)
   // RAFTMC_PROF=1: per-phase wall-clock ticks (100 MHz) of orig_dedup, summed over workgroups
   const bool prof_ = std::getenv("RAFTMC_PROF") != nullptr;

@@ -2,7 +2,7 @@
 //   raftmc [-config F.cfg] [-workers N] [-deadlock] [-depth D] [-device K]
 //          [-fptable BYTES] [-store BYTES] [-seed S] [-no-inv-oom] [-no-disjunct-copies] [-dump FILE] [-json]
 //          [-checkpoint LEVELS] [-checkpoint-file FILE] [-recover FILE] [-symmetry tlc|orbit]
-//          [-gpus N] [-countfinal] [-simulate [num=N]] [-continue] F.tla
+//          [-gpus N] [-same-device] [-countfinal] [-simulate [num=N]] [-continue] F.tla
 // (-continue, tlc_membership: one search reports the first counterexample of every listed invariant --
 // raftmc's own semantics, not TLC's -continue, which prints every violating state; mc_set_continue)
 // (-simulate [num=N]: TLC's simulation mode for raft_original -- N seeded random walks of at most
@@ -11,11 +11,16 @@
 // (-countfinal, with -depth D and -workers N: the states at depth D are counted and checked, not
 // stored; mc_opts.count_final_level)
 // (-gpus N: the node's GPUs -device .. -device+N-1 share one search, owner-partitioned fingerprints,
-// one host thread per GPU over an in-process RCCL communicator; TLC's -workers keeps its meaning)
+// one host thread per GPU over an in-process RCCL communicator; TLC's -workers keeps its meaning.
+// -same-device: every rank on GPU -device, for trying the multi-GPU path on a one-GPU machine;
+// mc_opts.same_device)
 // (-checkpoint counts BFS levels where TLC counts minutes; the file defaults to states/raftmc.ckpt.
 // Both hand-compiled families and the generated path write and recover one; -recover takes a larger
 // -fptable / -store than the writer had, which is how a run that ended as "state store full" or
-// "seen-set full" goes on from its last checkpoint)
+// "seen-set full" goes on from its last checkpoint.  raft_original also checkpoints with -gpus N -- the
+// file is then a manifest beside one file per GPU, FILE.g<levels>.r<rank> -- and -recover takes such a
+// checkpoint, or a single-GPU one, at any -gpus: a search that filled one GPU goes on on 2, 4 or 8,
+// one cut short on 8 on the 4 that are free)
 // Prints TLC-style lines and exits with TLC-like codes (0 ok, 12 safety
 // violation, 11 deadlock, 75 error).
 #include <cstdio>
@@ -47,6 +52,7 @@ int main(int argc, char** argv) {
     else if (k == "-countfinal") o.count_final_level = 1;
     else if (k == "-device") o.device = std::atoi(val());
     else if (k == "-gpus") o.n_gpus = std::atoi(val());
+    else if (k == "-same-device") o.same_device = 1;
     else if (k == "-frontend") {   // "auto" (default), "generated" (the SANY-subset front end for any module), "hand"
       const std::string v = val();
       o.frontend = v == "generated" ? MC_FRONTEND_GENERATED : v == "hand" ? MC_FRONTEND_HAND : MC_FRONTEND_AUTO;

@@ -225,13 +225,16 @@ class ModelChecker:
             raise RaftMCError(rc, self.lib.mc_last_error(self.h).decode())
 
     def set_checkpoint(self, path, every_levels=1):
-        """TLC -checkpoint: write the BFS state to `path` every `every_levels` levels (None: off)."""
+        """TLC -checkpoint: write the BFS state to `path` every `every_levels` levels (None: off).
+        raft_original with n_gpus > 1: `path` is a manifest beside one file per GPU,
+        path.g<levels>.r<rank> (include/raftmc.h mc_set_checkpoint)."""
         rc = self.lib.mc_set_checkpoint(self.h, path.encode() if path else None, every_levels if path else 0)
         if rc:
             raise RaftMCError(rc, self.lib.mc_last_error(self.h).decode())
 
     def set_recover(self, path):
-        """TLC -recover: the next run() resumes the search saved in `path`."""
+        """TLC -recover: the next run() resumes the search saved in `path`.  raft_original: a
+        single-GPU file or a multi-GPU manifest, on any n_gpus (a manifest on one GPU: workers != 1)."""
         rc = self.lib.mc_set_recover(self.h, path.encode() if path else None)
         if rc:
             raise RaftMCError(rc, self.lib.mc_last_error(self.h).decode())
