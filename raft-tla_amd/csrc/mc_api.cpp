@@ -152,6 +152,8 @@ int mc_open(const char* tla_path, const char* cfg_path, const mc_opts* o, mc_ctx
     }
     rmc::CfgFile cfg = rmc::parse_cfg_text(rmc::read_text_file(cfg_path));
     if (!cfg.symmetry.empty()) cfg.symmetry_def = rmc::definition_text(tla_path, cfg.symmetry);
+    if (fam == "raft_original")
+      for (const auto& n : cfg.invariants) cfg.invariant_defs.push_back(rmc::definition_text(tla_path, n));
     // count_final_level exists for raft_original's -workers N search with a depth bound (single GPU
     // or sharded): anywhere else it would be silently ignored, so it is refused
     if (o->count_final_level && (fam != "raft_original" || o->workers == 1 || o->max_depth <= 0))

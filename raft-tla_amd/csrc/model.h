@@ -38,6 +38,10 @@ struct CfgFile {
   // comments removed ("" = no such definition); filled by mc_open (tla_value.h definition_text)
   std::string symmetry_def;
   std::vector<std::string> constraints, action_constraints, invariants, properties;
+  // per INVARIANT name, in the same order: the body of its definition found the same way ("" = the
+  // module and the modules it EXTENDS do not define it); filled by mc_open for raft_original, whose
+  // safety invariants are accepted only from a module that states them (orig_model.cpp)
+  std::vector<std::string> invariant_defs;
   bool has(const std::string& n) const;
   const CVal& get(const std::string& n) const;
 };

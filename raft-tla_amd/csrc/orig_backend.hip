@@ -381,7 +381,7 @@ __global__ void __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(S::NW <
 // record order inside a region is immaterial: the FIFO merge keeps the minimum key, the -workers N
 // filter decides by key).
 template <class S>
-__global__ void __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(S::NW <= 15 ? 4 : 1))) orig_generate_lead(GenArgs a) {
+__global__ void __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(S::LEAD_WAVES))) orig_generate_lead(GenArgs a) {
   using W = typename S::Work;
   constexpr int NW = S::NW, NWP = (S::NW + 3) & ~3;
   __shared__ unsigned int lds_cnt[OA_NACT + 1];
@@ -1403,6 +1403,11 @@ template <class S>
 class OrigGpu : public Backend {
  public:
   using W = typename S::Work;
+  // S with the safety invariants (orig_spec.h §12) compiled into violated / inv_frame: what the host
+  // evaluates, and the instantiation of every kernel that checks invariants when the cfg lists one
+  // of them (safety()); a run that lists none launches the <S> kernels, whose code holds none of it
+  using SS = WithSafety<S>;
+  bool safety() const { return (m_.rt.invariants & OI_SAFETY_MASK) != 0; }
   static constexpr int NWP = (S::NW + 3) & ~3;
   explicit OrigGpu(const OrigModel& m) : m_(m) {}
   ~OrigGpu() override { release(); }
@@ -1537,13 +1542,18 @@ class OrigGpu : public Backend {
   // device); K_LEAD must be zero before (level start: orig_reset_ctr, later chunks: orig_advance, or
   // on a pipelined level the generate stream's own re-arm)
   void launch_generate(const GenArgs& g, unsigned nblk, hipStream_t st) {
+    if (safety()) launch_generate_as<SS>(g, nblk, st);
+    else launch_generate_as<S>(g, nblk, st);
+  }
+  template <class K>   // K: S or SS
+  void launch_generate_as(const GenArgs& g, unsigned nblk, hipStream_t st) {
     if (m_.rt.symmetry) {   // orbit fingerprints, every instance in one kernel (orig_sym.hip)
-      hipLaunchKernelGGL((orig_generate_sym<S>), dim3(nblk), dim3(BS), 0, st, g);
+      hipLaunchKernelGGL((orig_generate_sym<K>), dim3(nblk), dim3(BS), 0, st, g);
       return;
     }
-    hipLaunchKernelGGL((orig_generate<S>), dim3(nblk), dim3(BS), 0, st, g);
+    hipLaunchKernelGGL((orig_generate<K>), dim3(nblk), dim3(BS), 0, st, g);
     const unsigned lblk = std::min<unsigned>(nblk, std::max<unsigned>(64u, nblk / 8));
-    hipLaunchKernelGGL((orig_generate_lead<S>), dim3(lblk), dim3(BS), 0, st, g);
+    hipLaunchKernelGGL((orig_generate_lead<K>), dim3(lblk), dim3(BS), 0, st, g);
   }
 
   RouteArgs route_args(u32 world) const {
@@ -1579,7 +1589,9 @@ class OrigGpu : public Backend {
     return m;
   }
   void launch_materialize_plain(const MatPlainArgs& m, u64 cnt) {
-    hipLaunchKernelGGL((orig_materialize_plain<S>), dim3((unsigned)std::min<u64>(4096, (cnt * 2 + BS - 1) / BS)), dim3(BS), 0, stream_, m);
+    const dim3 grid((unsigned)std::min<u64>(4096, (cnt * 2 + BS - 1) / BS));
+    if (safety()) hipLaunchKernelGGL((orig_materialize_plain<SS>), grid, dim3(BS), 0, stream_, m);
+    else hipLaunchKernelGGL((orig_materialize_plain<S>), grid, dim3(BS), 0, stream_, m);
   }
 
   // ---------------------------------------------------------------- sharded stages
@@ -1683,7 +1695,11 @@ class OrigGpu : public Backend {
       m.seed = sres_.seed; m.rt = m_.rt; m.ctr = (unsigned long long*)d_ctr_;
       m.st_states = nullptr; m.st_meta = nullptr; m.st_dst = 0; m.st_cap = 0; m.store = last ? 0u : 1u;
       if (r == own && !last) { m.st_states = store_.states(); m.st_meta = store_.meta(); m.st_dst = own_dst; m.st_cap = store_.cap(); }
-      if (int rc = timed(3, [&] { hipLaunchKernelGGL((orig_materialize_sh<S>), dim3((unsigned)((m.n + BS - 1) / BS)), dim3(BS), 0, stream_, m); }, err))
+      const dim3 grid((unsigned)((m.n + BS - 1) / BS));
+      if (int rc = timed(3, [&] {
+            if (safety()) hipLaunchKernelGGL((orig_materialize_sh<SS>), grid, dim3(BS), 0, stream_, m);
+            else hipLaunchKernelGGL((orig_materialize_sh<S>), grid, dim3(BS), 0, stream_, m);
+          }, err))
         return rc;
     }
     sres_.kernels[3].algo_bytes += (double)total * (8 + NWP * 4 + (last ? 0 : SBW));
@@ -1728,8 +1744,8 @@ class OrigGpu : public Backend {
   int sim_walk(const RunOpts& o, int64_t walk, std::string& text, std::string& err) override {
     if (int rc = sim_check(o, err)) return rc;
     if (walk < 0 || walk >= SIM_MAX_WALKS) { err = "simulation: walk number out of range"; return MC_E_INVALID; }
-    SimWalk<S> w;
-    sim_replay<S>(m_.rt, o.inv_out_of_model, o.check_deadlock, o.seed, (u64)walk, sim_depth(o), w);
+    SimWalk<SS> w;
+    sim_replay<SS>(m_.rt, o.inv_out_of_model, o.check_deadlock, o.seed, (u64)walk, sim_depth(o), w);
     text.clear();
     for (const W& st : w.states) { text += state_text(st, false); text += "\n"; }
     return 0;
@@ -1751,7 +1767,7 @@ class OrigGpu : public Backend {
     W s0; S::init(s0);
     r.depth = 1;   // generated: the successors evaluated along the walks (Init is not counted)
     if (!S::in_model(s0, m_.rt)) { err = "the initial state violates a state constraint"; r.verdict = MC_VERDICT_OK; return 0; }
-    if (u32 bad = S::violated(s0, m_.rt.invariants)) {
+    if (u32 bad = SS::violated(s0, m_.rt.invariants)) {
       r.verdict = MC_VERDICT_INVARIANT_VIOLATION; r.violated = first_violated(bad);
       r.trace.push_back({"<Initial predicate>", state_text(s0, true)});
       r.seconds_total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -1772,7 +1788,9 @@ class OrigGpu : public Backend {
       a.walk0 = w0; a.nwalks = n; a.seed = o.seed; a.depth = depth; a.rt = m_.rt;
       a.inv_oom = o.inv_out_of_model ? 1u : 0u; a.deadlock = o.check_deadlock ? 1u : 0u; a.ctr = d.ctr;
       HIPCHK(hipEventRecord(d.e0, nullptr));
-      hipLaunchKernelGGL((orig_simulate<S>), dim3((unsigned)((n + BS - 1) / BS)), dim3(BS), 0, nullptr, a);
+      const dim3 grid((unsigned)((n + BS - 1) / BS));
+      if (safety()) hipLaunchKernelGGL((orig_simulate<SS>), grid, dim3(BS), 0, nullptr, a);
+      else hipLaunchKernelGGL((orig_simulate<S>), grid, dim3(BS), 0, nullptr, a);
       HIPCHK(hipGetLastError());
       HIPCHK(hipEventRecord(d.e1, nullptr));
       HIPCHK(hipMemcpy(h, d.ctr, sizeof h, hipMemcpyDeviceToHost));
@@ -1800,8 +1818,8 @@ class OrigGpu : public Backend {
     if (event != ~0ull) {
       // the winning walk again, on the host, with the same spec code and draws
       const u64 walk = sim_event_walk(event);
-      SimWalk<S> w;
-      sim_replay<S>(m_.rt, o.inv_out_of_model, o.check_deadlock, o.seed, walk, depth, w);
+      SimWalk<SS> w;
+      sim_replay<SS>(m_.rt, o.inv_out_of_model, o.check_deadlock, o.seed, walk, depth, w);
       if (w.event != event) {
         err = "simulation: the host replay of walk " + std::to_string(walk) + " does not reproduce the device's event";
         return MC_E_STATE;
@@ -1810,7 +1828,7 @@ class OrigGpu : public Backend {
       const u32 kind = sim_event_kind(event);
       if (kind == EV_VIOLATION) {
         r.verdict = MC_VERDICT_INVARIANT_VIOLATION;
-        r.violated = first_violated(S::violated(w.states.back(), m_.rt.invariants));
+        r.violated = first_violated(SS::violated(w.states.back(), m_.rt.invariants));
       } else if (kind == EV_DEADLOCK) {
         r.verdict = MC_VERDICT_DEADLOCK;
       } else {
@@ -1986,7 +2004,7 @@ class OrigGpu : public Backend {
     r.generated = 1; r.distinct = 1; store_.set_total(1);
     r.levels.push_back({1, 1, 0.0});
     r.depth = 1;
-    const u32 bad = S::violated(s0, m_.rt.invariants);
+    const u32 bad = SS::violated(s0, m_.rt.invariants);
     ended = !S::in_model(s0, m_.rt) || bad;
     if (ended) HIPCHK(hipStreamSynchronize(stream_));   // the run ends here
     if (!S::in_model(s0, m_.rt)) { err = "the initial state violates a state constraint"; r.verdict = MC_VERDICT_OK; r.distinct = 0; return 0; }
@@ -2135,7 +2153,8 @@ class OrigGpu : public Backend {
     m.states = store_.states(); m.meta = store_.meta(); m.chunk_begin = cb - store_.base(); m.chunk_count = cnt; m.gid0 = cb;
     m.winmask = d_winmask_; m.woff = d_woff_; m.ww = WW; m.dst_base = s.level_end() - store_.base(); m.cap = store_.cap();
     m.rt = m_.rt; m.ctr = (unsigned long long*)d_ctr_;
-    hipLaunchKernelGGL((orig_materialize<S>), dim3(nblk), dim3(BS), 0, stream_, m);
+    if (safety()) hipLaunchKernelGGL((orig_materialize<SS>), dim3(nblk), dim3(BS), 0, stream_, m);
+    else hipLaunchKernelGGL((orig_materialize<S>), dim3(nblk), dim3(BS), 0, stream_, m);
     return 0;
   }
 
@@ -2314,7 +2333,7 @@ class OrigGpu : public Backend {
     W t;
     const int act = successor(s, (int)k, t);
     r.verdict = MC_VERDICT_INVARIANT_VIOLATION;
-    r.violated = first_violated(S::violated(t, m_.rt.invariants));
+    r.violated = first_violated(SS::violated(t, m_.rt.invariants));
     r.depth += 1;
     build_trace(pg, act >= 0 ? kOrigActNames[act] : "?", t, r, err);
     if (progress_) std::fprintf(stderr, "trace of %zu states: %.3f s\n", r.trace.size(), since());
@@ -2619,7 +2638,7 @@ class OrigGpu : public Backend {
     sres_.generated = 1; sres_.distinct = 1; sres_.depth = 1;
     sres_.levels.push_back({1, 0, 0.0});
     if (!S::in_model(s0, m_.rt)) { err = "the initial state violates a state constraint"; return MC_E_UNSUPPORTED; }
-    if (S::violated(s0, m_.rt.invariants)) { err = "the initial state violates an invariant"; return MC_E_UNSUPPORTED; }
+    if (SS::violated(s0, m_.rt.invariants)) { err = "the initial state violates an invariant"; return MC_E_UNSUPPORTED; }
     sh_next_write_ = store_.total();
     return 0;
   }
@@ -2763,7 +2782,7 @@ class OrigGpu : public Backend {
         if (hipMemcpy(w, store_.states() + par * NWP, NWP * 4, hipMemcpyDeviceToHost) == hipSuccess) {
           W s, t; S::unpack(w, s);
           const int act = successor(s, k, t);
-          sviol_bad_ = S::violated(t, m_.rt.invariants);
+          sviol_bad_ = SS::violated(t, m_.rt.invariants);
           sviol_parent_ = ((u64)rank_ << 37) | par; sviol_act_ = act >= 0 ? kOrigActNames[act] : "?";
           sviol_text_ = state_text(t, true);
         }
@@ -3141,6 +3160,7 @@ class OrigGpu : public Backend {
 #else
 #define RMC_ORIG_SHAPES(X) \
   X(3, 1, 2, 1, 2) /* C1 */ \
+  X(3, 1, 2, 1, 6) /* safety_trio6: the smallest 3-server model with a commit */ \
   X(3, 2, 3, 2, 5) /* C2 */ \
   X(3, 2, 3, 2, 6)          \
   X(3, 2, 3, 2, 4)          \

@@ -62,9 +62,16 @@ OrigModel resolve_orig_model(const CfgFile& cfg) {
   }
   if (m.rt.constraints != (OC_BoundedTerms | OC_BoundedLogs | OC_BoundedMessages))
     throw CfgError(MC_E_UNSUPPORTED, "raft_original needs BoundedTerms, BoundedLogs and BoundedMessages (its state space is infinite otherwise, G1)");
-  for (auto& n : cfg.invariants) {
-    if (const u32 bit = orig_inv_bit(n.c_str())) m.rt.invariants |= bit;
-    else throw CfgError(MC_E_UNSUPPORTED, "unknown invariant '" + n + "' for raft_original");
+  for (size_t k = 0; k < cfg.invariants.size(); ++k) {
+    const std::string& n = cfg.invariants[k];
+    const u32 bit = orig_inv_bit(n.c_str());
+    if (!bit) throw CfgError(MC_E_UNSUPPORTED, "unknown invariant '" + n + "' for raft_original");
+    // a safety invariant is compiled from configs/raft_original_safety_mc.tla's text: accepted only
+    // when the root module, or a module it EXTENDS, states it
+    if ((bit & OI_SAFETY_MASK) && (k >= cfg.invariant_defs.size() || cfg.invariant_defs[k].empty()))
+      throw CfgError(MC_E_UNSUPPORTED, "invariant '" + n + "': the module and the modules it EXTENDS do not define " + n +
+                                       " (configs/raft_original_safety_mc.tla defines the log- and commit-safety invariants)");
+    m.rt.invariants |= bit;
     m.inv_names.push_back(n);
   }
   return m;

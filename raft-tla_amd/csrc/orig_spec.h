@@ -38,11 +38,24 @@ static const char* const kOrigActNames[OA_NACT] = {
 
 // constraint / invariant selection bits (resolved from cfg names on the host)
 enum { OC_BoundedTerms = 1, OC_BoundedLogs = 2, OC_BoundedMessages = 4 };
-enum { OI_ElectionSafety = 1, OI_LogMatching = 2, OI_NoLeader = 4, OI_NoCommit = 8 };
-static const char* const kOrigInvNames[4] = {"ElectionSafety", "LogMatching", "NoLeader", "NoCommit"};
-// OI_* bit of an invariant name (configs/raft_original_mc.tla), 0 if unknown
+enum { OI_ElectionSafety = 1, OI_LogMatching = 2, OI_NoLeader = 4, OI_NoCommit = 8,
+       // the log- and commit-side safety invariants of configs/raft_original_safety_mc.tla (§12 below)
+       OI_CommitWithinLog = 1 << 4, OI_LeaderVotesQuorum = 1 << 5, OI_CandidateTermNotInLog = 1 << 6,
+       OI_LeaderHasLatestOfTerm = 1 << 7, OI_VotesGrantedInv = 1 << 8, OI_QuorumLogInv = 1 << 9,
+       OI_MoreUpToDateCorrect = 1 << 10, OI_LeaderCompleteness = 1 << 11, OI_StateMachineSafety = 1 << 12,
+       OI_AllHaveCommitted_false = 1 << 13 };
+// the bits S::violated leaves to S::violated_safety: a run that lists none of them launches the
+// kernels compiled without that code (WithSafety below)
+constexpr u32 OI_SAFETY_MASK = 0x3ff0u;
+constexpr int kOrigInvCount = 14;
+static const char* const kOrigInvNames[kOrigInvCount] = {
+    "ElectionSafety", "LogMatching", "NoLeader", "NoCommit", "CommitWithinLog", "LeaderVotesQuorum", "CandidateTermNotInLog",
+    "LeaderHasLatestOfTerm", "VotesGrantedInv", "QuorumLogInv", "MoreUpToDateCorrect", "LeaderCompleteness", "StateMachineSafety",
+    "AllHaveCommitted_false"};
+// OI_* bit of an invariant name (configs/raft_original_mc.tla, the OI_SAFETY_MASK ones
+// configs/raft_original_safety_mc.tla), 0 if unknown
 inline u32 orig_inv_bit(const char* n) {
-  for (int k = 0; k < 4; ++k) {
+  for (int k = 0; k < kOrigInvCount; ++k) {
     const char* a = kOrigInvNames[k]; const char* b = n;
     while (*a && *a == *b) { ++a; ++b; }
     if (!*a && !*b) return 1u << k;
@@ -115,6 +128,8 @@ struct Orig {
   // second pass runs it on full waves of just those parents (leader_work)
   static constexpr int LEAD_LO = 2 * N + N * N, LEAD_HI = LEAD_LO + N + N * NV + N + N * N;
   static constexpr int I_RECV = LEAD_HI, I_DUP = I_RECV + MK, I_DROP = I_DUP + MK;   // Receive / Duplicate / Drop
+  // orig_generate_lead's occupancy hint (waves per SIMD; orig_backend.hip): 4 for states of <= 15 words
+  static constexpr int LEAD_WAVES = NW <= 15 ? 4 : 1;
 
   static_assert(N >= 1 && N <= 7, "N");
   static_assert(N * TB <= 32 && N * VB <= 32 && N * CIB <= 32 && N * N <= 32, "scalar field words");
@@ -691,6 +706,186 @@ struct Orig {
     return m;
   }
 
+  // ---------------------------------------------------------------- §12 log- and commit-side safety
+  // The invariants of configs/raft_original_safety_mc.tla (tlc_membership/raft.tla:969-1099 restated
+  // over raft_original's variables), evaluated on the packed fields: a log is one word (length in the
+  // low LLB bits, then one EB-bit entry code per position), so
+  //   PrefixOf(Committed(i), log[j])  is  CommittedLen(i) <= Len(log[j]) and one masked compare of the
+  //                                   two log words over the first CommittedLen(i) entry fields;
+  //   "every quorum meets H"          (QuorumLogInv, H = the servers that hold the prefix) is
+  //                                   2 * |H| >= N: the complement of H is then no quorum -- a popcount,
+  //                                   no subset is enumerated;
+  //   the vote sets of LeaderVotesQuorum / CandidateTermNotInLog are popcounts over per-server compares
+  //                                   of the term and votedFor fields;
+  //   MaxOrZero({n : log[n].term = T}) is the last position of term T in the log word (last_of_term).
+  // Every server index below is a compile-time constant after unrolling (no runtime-indexed array).
+  // None of this is reached from S::violated: a kernel gets it through WithSafety<S> only.
+  RMC_HD static u32 prefix_mask(int c) { return ((1u << (c * EB)) - 1u) << LLB; }   // entry fields 0..c-1, c <= ML + 1
+  RMC_HD static u32 log_terms(u32 lw) {   // bit T set: the log holds an entry of term T
+    const int n = llen(lw);
+    u32 m = 0;
+#pragma unroll
+    for (int p = 0; p < ML + 1; ++p) m |= p < n ? 1u << eterm(lent(lw, p)) : 0u;
+    return m;
+  }
+  RMC_HD static int last_of_term(u32 lw, int term) {   // MaxOrZero({n \in DOMAIN log : log[n].term = term})
+    const int n = llen(lw);
+    int r = 0;
+#pragma unroll
+    for (int p = 0; p < ML + 1; ++p) r = (p < n && eterm(lent(lw, p)) == term) ? p + 1 : r;
+    return r;
+  }
+  RMC_HD static u32 violated_safety(const Work& t, u32 invs) {
+    if (!(invs & OI_SAFETY_MASK)) return 0;
+    int len[N], cl[N], tm[N];
+    u32 hold[N];   // hold[i] bit j: PrefixOf(Committed(i), log[j])
+    bool within = true;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+      const int ci = g_commit(t, i);
+      len[i] = llen(t.log.v[i]); tm[i] = g_term(t, i);
+      cl[i] = ci <= len[i] ? ci : len[i];                         // CommittedLen(i)
+      within &= ci <= len[i];
+    }
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+      const u32 m = prefix_mask(cl[i]);
+      u32 h = 0;
+#pragma unroll
+      for (int j = 0; j < N; ++j) h |= (cl[i] <= len[j] && ((t.log.v[i] ^ t.log.v[j]) & m) == 0u) ? 1u << j : 0u;
+      hold[i] = h;
+    }
+    u32 bad = 0;
+    if ((invs & OI_CommitWithinLog) && !within) bad |= OI_CommitWithinLog;
+    if (invs & OI_LeaderVotesQuorum) {          // raft.tla:988-993
+      bool ok = true;
+#pragma unroll
+      for (int i = 0; i < N; ++i) {
+        u32 q = 0;
+#pragma unroll
+        for (int j = 0; j < N; ++j) q |= (tm[j] > tm[i] || (tm[j] == tm[i] && g_voted(t, j) == i)) ? 1u << j : 0u;
+        ok &= g_st(t, i) != (int)L || popc32(q) * 2 > N;
+      }
+      if (!ok) bad |= OI_LeaderVotesQuorum;
+    }
+    if (invs & OI_CandidateTermNotInLog) {      // raft.tla:997-1004
+      u32 terms = 0;
+#pragma unroll
+      for (int j = 0; j < N; ++j) terms |= log_terms(t.log.v[j]);
+      bool ok = true;
+#pragma unroll
+      for (int i = 0; i < N; ++i) {
+        u32 q = 0;
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+          const int v = g_voted(t, j);
+          q |= (tm[j] == tm[i] && (v == i || v == N)) ? 1u << j : 0u;
+        }
+        ok &= !(g_st(t, i) == (int)C && popc32(q) * 2 > N) || ((terms >> tm[i]) & 1u) == 0u;
+      }
+      if (!ok) bad |= OI_CandidateTermNotInLog;
+    }
+    if (invs & OI_LeaderHasLatestOfTerm) {      // raft.tla:1009-1014
+      bool ok = true;
+#pragma unroll
+      for (int i = 0; i < N; ++i) {
+        const int mine = last_of_term(t.log.v[i], tm[i]);
+        bool all = true;
+#pragma unroll
+        for (int j = 0; j < N; ++j) all &= mine >= last_of_term(t.log.v[j], tm[i]);
+        ok &= g_st(t, i) != (int)L || all;
+      }
+      if (!ok) bad |= OI_LeaderHasLatestOfTerm;
+    }
+    if (invs & OI_VotesGrantedInv) {            // raft.tla:1048-1052
+      bool ok = true;
+#pragma unroll
+      for (int i = 0; i < N; ++i) {
+        const int v = g_voted(t, i);
+        ok &= v == N || ((hold[i] >> v) & 1u) != 0u;
+      }
+      if (!ok) bad |= OI_VotesGrantedInv;
+    }
+    if (invs & OI_QuorumLogInv) {               // raft.tla:1056-1060
+      bool ok = true;
+#pragma unroll
+      for (int i = 0; i < N; ++i) ok &= popc32(hold[i]) * 2 >= N;
+      if (!ok) bad |= OI_QuorumLogInv;
+    }
+    if (invs & OI_MoreUpToDateCorrect) {        // raft.tla:1066-1071
+      bool ok = true;
+#pragma unroll
+      for (int i = 0; i < N; ++i)
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+          const int li = last_term(t.log.v[i]), lj = last_term(t.log.v[j]);
+          const bool upto = li > lj || (li == lj && len[i] >= len[j]);
+          ok &= !upto || ((hold[j] >> i) & 1u) != 0u;
+        }
+      if (!ok) bad |= OI_MoreUpToDateCorrect;
+    }
+    if (invs & OI_LeaderCompleteness) {         // raft.tla:1089-1099
+      bool ok = true;
+#pragma unroll
+      for (int i = 0; i < N; ++i)
+#pragma unroll
+        for (int p = 0; p < ML + 1; ++p) {
+          const int e = lent(t.log.v[i], p);
+#pragma unroll
+          for (int l = 0; l < N; ++l)
+            ok &= !(p < cl[i] && g_st(t, l) == (int)L && tm[l] > eterm(e)) || (p < len[l] && lent(t.log.v[l], p) == e);
+        }
+      if (!ok) bad |= OI_LeaderCompleteness;
+    }
+    if (invs & OI_StateMachineSafety) {
+      bool ok = true;
+#pragma unroll
+      for (int i = 0; i < N; ++i)
+#pragma unroll
+        for (int j = i + 1; j < N; ++j) {
+          const int c = cl[i] < cl[j] ? cl[i] : cl[j];
+          ok &= ((t.log.v[i] ^ t.log.v[j]) & prefix_mask(c)) == 0u;
+        }
+      if (!ok) bad |= OI_StateMachineSafety;
+    }
+    if (invs & OI_AllHaveCommitted_false) {     // test-only control
+      bool ok = true;
+#pragma unroll
+      for (int i = 0; i < N; ++i) ok &= hold[i] == (u32)lomask(N);
+      if (!ok) bad |= OI_AllHaveCommitted_false;
+    }
+    return bad;
+  }
+
+  // inv_frame for the safety invariants: the actions that write a variable the invariant reads.
+  //   commitIndex   Restart :173, AdvanceCommitIndex :274, HandleAppendEntriesRequest :363
+  //   log           ClientRequest :250, HandleAppendEntriesRequest :380 (conflict), :385 (append)
+  //   state         Restart :167, Timeout :178, BecomeLeader :231, UpdateTerm :408,
+  //                 HandleAppendEntriesRequest :348 (a Candidate steps down)
+  //   currentTerm   Timeout :179, UpdateTerm :407
+  //   votedFor      Timeout :182, UpdateTerm :409, HandleRequestVoteRequest :291
+  // CommitWithinLog, QuorumLogInv, MoreUpToDateCorrect, StateMachineSafety and AllHaveCommitted_false
+  // read commitIndex and log; VotesGrantedInv also votedFor; LeaderCompleteness commitIndex, log,
+  // state and currentTerm; LeaderVotesQuorum state, currentTerm and votedFor; CandidateTermNotInLog
+  // those three and log; LeaderHasLatestOfTerm state, currentTerm and log.
+  RMC_HD static u32 inv_frame_safety(int act) {
+    const bool w_commit = act == OA_Restart || act == OA_AdvanceCommitIndex || act == OA_HandleAppendEntriesRequest;
+    const bool w_log = act == OA_ClientRequest || act == OA_HandleAppendEntriesRequest;
+    const bool w_state = act == OA_Restart || act == OA_Timeout || act == OA_BecomeLeader || act == OA_UpdateTerm ||
+                         act == OA_HandleAppendEntriesRequest;
+    const bool w_term = act == OA_Timeout || act == OA_UpdateTerm;
+    const bool w_voted = act == OA_Timeout || act == OA_UpdateTerm || act == OA_HandleRequestVoteRequest;
+    u32 m = 0;
+    if (w_commit || w_log)
+      m |= OI_CommitWithinLog | OI_QuorumLogInv | OI_MoreUpToDateCorrect | OI_StateMachineSafety | OI_AllHaveCommitted_false;
+    if (w_commit || w_log || w_voted) m |= OI_VotesGrantedInv;
+    if (w_commit || w_log || w_state || w_term) m |= OI_LeaderCompleteness;
+    if (w_state || w_term || w_voted) m |= OI_LeaderVotesQuorum;
+    if (w_state || w_term || w_voted || w_log) m |= OI_CandidateTermNotInLog;
+    if (w_state || w_term || w_log) m |= OI_LeaderHasLatestOfTerm;
+    return m;
+  }
+
   // ---------------------------------------------------------------- pack / unpack (canonical stored form)
   RMC_HD static void pack(const Work& t, u32 (&w)[NW]) {
     BitOut<NW> o;
@@ -824,6 +1019,11 @@ struct Orig {
   // every invariant compiled here commute with a permutation of Server.  A permutation pi is a
   // word of 3 bits per server, pi(i) = (pi >> 3i) & 7 = the image of server i.  Value is not
   // permuted, so logs, log universe indices and allLogs are fixed by every pi.
+  // The safety invariants (violated_safety above) are permutation-invariant too: each quantifies over
+  // all of Server (and Quorum, a set of subsets closed under renaming), names no particular server,
+  // and reads votedFor only through "= i", "= j" and "\in {i, Nil}" with i, j bound -- renaming
+  // the servers renames the bound variables and leaves every truth value as it was.  So under SYMMETRY
+  // checking the kept member of an orbit checks the orbit.
   static constexpr int NPERM = perm_count(N);
   RMC_HD static int pi_of(u32 pi, int i) { return (int)((pi >> (3 * i)) & 7u); }
   // the p-th permutation in Lehmer order, 0 <= p < N! (arithmetic only: no table)
@@ -1014,6 +1214,21 @@ struct Orig {
     const u64 fp = fmix64((best + base) ^ seed);
     return fp ? fp : 1ull;
   }
+};
+
+// B with the safety invariants compiled in: violated / inv_frame cover the OI_SAFETY_MASK bits as
+// well.  The kernels are templates over the spec type, so orig_generate<WithSafety<S>> is the
+// instantiation a run launches when its cfg lists a safety invariant, and orig_generate<S> --
+// whose code holds none of violated_safety -- stays what every other run launches.
+template <class B>
+struct WithSafety : B {
+  using Work = typename B::Work;
+  // the leader instances are where most safety frames meet (BecomeLeader, ClientRequest,
+  // AdvanceCommitIndex): at 4 waves per SIMD (128 VGPRs) C2's orig_generate_lead spilled 8 bytes; 3
+  // (168) holds it, for the ~1% of parents with leader work
+  static constexpr int LEAD_WAVES = B::NW <= 15 ? 3 : 1;
+  RMC_HD static u32 violated(const Work& t, u32 invs) { return B::violated(t, invs) | B::violated_safety(t, invs); }
+  RMC_HD static u32 inv_frame(int act) { return B::inv_frame(act) | B::inv_frame_safety(act); }
 };
 
 }  // namespace rmc
