@@ -22,6 +22,7 @@
 
 #include "../../include/raftmc.h"
 #include "backend.h"
+#include "dev_owner.h"
 #include "shard_transport.h"
 
 namespace rmc {
@@ -38,41 +39,38 @@ struct FifoShardLoop {
   static constexpr int NST = MC_SHARD_NSTAT;
   static constexpr int SMALL = 32 + 2 * MC_SHARD_NSTAT;
 
+  DevOwner<HipDevApi> res;       // owns the stream and the four buffers above; frees them when the loop goes
+
   FifoShardLoop(Backend& b, ShardTransport& t, int rank, int world) : be(b), T(t), me(rank), W(world) {}
   ~FifoShardLoop() {
     if (s) (void)hipStreamSynchronize(s);
-    if (d_send) (void)hipFree(d_send);
-    if (d_recv) (void)hipFree(d_recv);
-    if (d_small) (void)hipFree(d_small);
-    if (h_small) (void)hipHostFree(h_small);
-    if (s) (void)hipStreamDestroy(s);
   }
 
-#define FSL_HIP(x)                                                     \
+#define LOOPCHK(x)                                                     \
   do {                                                                 \
-    if ((x) != hipSuccess) { err = std::string("HIP: ") + #x; return MC_E_NO_DEVICE; } \
+    hipError_t e_ = (x);                                               \
+    if (e_ != hipSuccess) { err = std::string("HIP: ") + #x; return MC_E_NO_DEVICE; } \
   } while (0)
 
+  // grow-only device buffer of cap bytes (what it held is not kept)
   int grow(char*& p, uint64_t& cap, uint64_t need, std::string& err) {
     if (need <= cap && p) return 0;
-    FSL_HIP(hipStreamSynchronize(s));
-    if (p) FSL_HIP(hipFree(p));
-    p = nullptr;
+    LOOPCHK(hipStreamSynchronize(s));
     cap = std::max<uint64_t>(need + need / 4, 1 << 20);
-    FSL_HIP(hipMalloc(&p, cap));
+    LOOPCHK(res.device(&p, cap));   // (frees the old one first)
     return 0;
   }
   // all-to-all of one int64 per peer: recv[r] = what rank r sends to me
   int counts(const int64_t* send, int64_t* recv, std::string& err) {
     for (int r = 0; r < W; ++r) h_small[r] = send[r];
-    FSL_HIP(hipMemcpyAsync(d_small, h_small, 8 * (uint64_t)W, hipMemcpyHostToDevice, s));
+    LOOPCHK(hipMemcpyAsync(d_small, h_small, 8 * (uint64_t)W, hipMemcpyHostToDevice, s));
     if (W > 1) {
       const char* src[8]; char* dst[8]; uint64_t n8[8];
       for (int r = 0; r < W; ++r) { src[r] = (const char*)(d_small + r); dst[r] = (char*)(d_small + 8 + r); n8[r] = 8; }
       if (T.exchange(me, W, src, n8, dst, n8, s, err)) return MC_E_NO_DEVICE;
     }
-    FSL_HIP(hipMemcpyAsync(h_small + 8, d_small + 8, 8 * (uint64_t)W, hipMemcpyDeviceToHost, s));
-    FSL_HIP(hipStreamSynchronize(s));
+    LOOPCHK(hipMemcpyAsync(h_small + 8, d_small + 8, 8 * (uint64_t)W, hipMemcpyDeviceToHost, s));
+    LOOPCHK(hipStreamSynchronize(s));
     for (int r = 0; r < W; ++r) recv[r] = r == me ? send[me] : h_small[8 + r];
     return 0;
   }
@@ -87,10 +85,10 @@ struct FifoShardLoop {
       if (is_max && is_max[k]) mx[k] = h[k], ++nmax;
     }
     for (int k = 0; k < n; ++k) h_small[32 + NST + k] = mx[k];
-    FSL_HIP(hipMemcpyAsync(d_sum, h_small + 32, 2 * NST * 8, hipMemcpyHostToDevice, s));
+    LOOPCHK(hipMemcpyAsync(d_sum, h_small + 32, 2 * NST * 8, hipMemcpyHostToDevice, s));
     if ((W > 1 || T.allreduce_at_world1()) && T.allreduce(d_sum, n, d_max, nmax ? n : 1, s, err)) return MC_E_NO_DEVICE;
-    FSL_HIP(hipMemcpyAsync(h_small + 32, d_sum, 2 * NST * 8, hipMemcpyDeviceToHost, s));
-    FSL_HIP(hipStreamSynchronize(s));
+    LOOPCHK(hipMemcpyAsync(h_small + 32, d_sum, 2 * NST * 8, hipMemcpyDeviceToHost, s));
+    LOOPCHK(hipStreamSynchronize(s));
     for (int k = 0; k < n; ++k) h[k] = is_max && is_max[k] ? h_small[32 + NST + k] : h_small[32 + k];
     return 0;
   }
@@ -115,9 +113,9 @@ struct FifoShardLoop {
       src[r] = d_send + (uint64_t)soff[r] * rb; sb[r] = (uint64_t)sc[r] * rb;
       dst[r] = d_recv + (uint64_t)roff[r] * rb; rbs[r] = (uint64_t)rc[r] * rb;
     }
-    if (sb[me]) FSL_HIP(hipMemcpyAsync(dst[me], src[me], sb[me], hipMemcpyDeviceToDevice, s));
+    if (sb[me]) LOOPCHK(hipMemcpyAsync(dst[me], src[me], sb[me], hipMemcpyDeviceToDevice, s));
     if (W > 1 && T.exchange(me, W, src, sb, dst, rbs, s, err)) return MC_E_NO_DEVICE;
-    FSL_HIP(hipStreamSynchronize(s));
+    LOOPCHK(hipStreamSynchronize(s));
     return 0;
   }
 
@@ -126,9 +124,9 @@ struct FifoShardLoop {
   }
 
   int run(std::string& err) {
-    FSL_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    FSL_HIP(hipMalloc(&d_small, SMALL * 8));
-    FSL_HIP(hipHostMalloc((void**)&h_small, SMALL * 8, hipHostMallocDefault));
+    LOOPCHK(res.stream(&s, hipStreamNonBlocking));
+    LOOPCHK(res.device(&d_small, SMALL * 8));
+    LOOPCHK(res.pinned(&h_small, SMALL * 8));
     bool flag_max[NST] = {false};
     for (int k = 3; k < 6; ++k) flag_max[k] = true;   // error flags, first event, deadlock (shard.py FLAG_SLICE)
     int64_t sc[8] = {0}, rc[8] = {0}, gat[8] = {0}, dummy[8] = {0};
@@ -188,7 +186,7 @@ struct FifoShardLoop {
     }
     return 0;
   }
-#undef FSL_HIP
+#undef LOOPCHK
 };
 
 }  // namespace rmc

@@ -902,24 +902,29 @@ class MembGpu : public Backend {
     } catch (const CfgError& e) { err = e.what(); return e.code; }
     return 0;
   }
+  // every prefix constraint of the cfg has its trace, or the refusal; hint: how the caller gets it one
+  static constexpr const char* kPrefixHint = ": place the reference's raft.tla next to the module, or pass the trace with mc_set_history_prefix";
+  int require_prefixes(std::string& err, const char* hint) const {
+    for (int q = 0; q < 2; ++q)
+      if (((m_.rt.constraints >> kPrefixCon[q]) & 1u) && !have_prefix_[q]) {
+        err = std::string(kMembConNames[kPrefixCon[q]]) + " needs its golden history trace" + hint;
+        return MC_E_UNSUPPORTED;
+      }
+    return 0;
+  }
   // runtime descriptors with the prefix tables: host copies for host-side re-derivation, device
   // copies for the kernels
   int prepare_prefixes(std::string& err) {
+    if (int rc = require_prefixes(err, kPrefixHint)) return rc;
     rt_host_ = m_.rt; rt_dev_ = m_.rt;
     u32 off = S::H_PREFIX;
     for (int r = 0; r < 2; ++r) {
       if (!((m_.rt.constraints >> kPrefixCon[r]) & 1u)) continue;
-      if (!have_prefix_[r]) {
-        err = std::string(kMembConNames[kPrefixCon[r]]) + " needs its golden history trace: place the reference's "
-              "raft.tla next to the module, or pass the trace with mc_set_history_prefix";
-        return MC_E_UNSUPPORTED;
-      }
       if (off + S::NB > 64) { err = "both punctuated-search prefix constraints at once do not fit the history word for this |Server|"; return MC_E_UNSUPPORTED; }
       if (r == 1) rt_host_.preg1_off = rt_dev_.preg1_off = off;
       off += S::NB;
-      if (d_ptab_[r]) { (void)hipFree(d_ptab_[r]); d_ptab_[r] = nullptr; }
       const size_t bytes = std::max<size_t>(16, ptab_[r].size() * 8);
-      HIPCHK(hipMalloc(&d_ptab_[r], bytes));
+      HIPCHK(res_.device(&d_ptab_[r], bytes));   // (frees the old one first)
       if (!ptab_[r].empty()) HIPCHK(hipMemcpy(d_ptab_[r], ptab_[r].data(), ptab_[r].size() * 8, hipMemcpyHostToDevice));
       const u32 len = plen_[r] ? plen_[r] : 0;
       if (r == 0) { rt_host_.ptab0 = ptab_[0].data(); rt_dev_.ptab0 = d_ptab_[0]; rt_host_.plen0 = rt_dev_.plen0 = len; }
@@ -979,349 +984,501 @@ class MembGpu : public Backend {
     chunk_ = std::max<u64>(BS, std::min<u64>({cap, (sb / 8) / (16 * (u64)S::NSLOT), (u64)SCAN_MAX_BLOCKS * BS}));
     chunk_ = (chunk_ / BS) * BS;
     table_mask_ = slots - 1;
-    HIPCHK(hipMalloc(&d_table_, slots * 16));
+    HIPCHK(res_.device(&d_table_, slots * 16));
     HIPCHK(store_.alloc(cap, NWP));
-    HIPCHK(hipMalloc(&d_cand_, chunk_ * S::NSLOT * 8));
-    HIPCHK(hipMalloc(&d_newrec_, chunk_ * S::NSLOT * 8));
-    HIPCHK(hipMalloc(&d_nsucc_, chunk_ * 2));
-    HIPCHK(hipMalloc(&d_cells_, chunk_ * S::NSLOT * 4));
-    HIPCHK(hipMalloc(&d_cells_oom_, chunk_ * S::NSLOT * 4));
-    HIPCHK(hipMalloc(&d_cell_count_, 8 * ((chunk_ + BS - 1) / BS) * 4));
-    HIPCHK(hipMalloc(&d_big_, chunk_ * S::NSLOT * 4));
-    HIPCHK(hipMalloc(&d_smask_, chunk_ * SMW * 8));
-    HIPCHK(hipMalloc(&d_woff_, chunk_ * 4));
-    HIPCHK(hipMalloc(&d_bsum_, SCAN_MAX_BLOCKS * 8));
-    HIPCHK(hipMalloc(&d_ctr_, C_NCTR * 8));
-    HIPCHK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
-    for (auto& e : ev_) HIPCHK(hipEventCreate(&e));
+    HIPCHK(res_.device(&d_cand_, chunk_ * S::NSLOT * 8));
+    HIPCHK(res_.device(&d_newrec_, chunk_ * S::NSLOT * 8));
+    HIPCHK(res_.device(&d_nsucc_, chunk_ * 2));
+    HIPCHK(res_.device(&d_cells_, chunk_ * S::NSLOT * 4));
+    HIPCHK(res_.device(&d_cells_oom_, chunk_ * S::NSLOT * 4));
+    HIPCHK(res_.device(&d_cell_count_, 8 * ((chunk_ + BS - 1) / BS) * 4));
+    HIPCHK(res_.device(&d_big_, chunk_ * S::NSLOT * 4));
+    HIPCHK(res_.device(&d_smask_, chunk_ * SMW * 8));
+    HIPCHK(res_.device(&d_woff_, chunk_ * 4));
+    HIPCHK(res_.device(&d_bsum_, SCAN_MAX_BLOCKS * 8));
+    HIPCHK(res_.device(&d_ctr_, C_NCTR * 8));
+    HIPCHK(res_.stream(&stream_, hipStreamNonBlocking));
     dev_ = o.device; req_table_ = o.fp_table_bytes; req_store_ = o.state_store_bytes;
     return 0;
   }
 
-  float ms(int a, int b) { float x = 0; (void)hipEventElapsedTime(&x, ev_[a], ev_[b]); return x; }
-
-  int run(const RunOpts& o, RunResult& r, std::string& err) override {
-    sharded_ = false;
-    const bool cont = o.continue_mode;
-    if (cont && (!o.checkpoint_path.empty() || !o.recover_path.empty() || o.sim_walks > 0)) {
-      err = "continue mode: not with a checkpoint or recover path, nor with simulation";
-      return MC_E_UNSUPPORTED;
-    }
-    for (int q = 0; q < 2; ++q)
-      if (((m_.rt.constraints >> kPrefixCon[q]) & 1u) && !have_prefix_[q]) {
-        err = std::string(kMembConNames[kPrefixCon[q]]) + " needs its golden history trace: place the reference's "
-              "raft.tla next to the module, or pass the trace with mc_set_history_prefix";
-        return MC_E_UNSUPPORTED;
-      }
-    if (int rc = ensure_alloc(o, err)) return rc;
-    if (int rc = prepare_prefixes(err)) return rc;
-    rt_host_.sym_tlc = rt_dev_.sym_tlc = (o.sym_tlc && m_.rt.symmetry) ? 1u : 0u;
-    fp_slice_test_ = o.test_fp_slice;
-    rt_host_.disjunct_copies = rt_dev_.disjunct_copies = o.disjunct_copies ? 1u : 0u;
-    auto t0 = std::chrono::steady_clock::now();
-    HIPCHK(hipMemsetAsync(d_table_, 0, (table_mask_ + 1) * 16, stream_));
-    HIPCHK(hipStreamSynchronize(stream_));
-    r = RunResult();
-    r.seed = o.seed ? o.seed : 0x5EED5EED2024ull;
+  // ---------------------------------------------------------------- set-up shared by run() and shard_open
+  static RunResult new_result(u64 seed, std::initializer_list<const char*> kernels) {
+    RunResult r;
+    r.seed = seed ? seed : 0x5EED5EED2024ull;
     r.state_bytes = NWP * 4;
     for (int k = 0; k < MA_NACT; ++k) r.action_names.push_back(kMembActNames[k]);
     r.act_generated.assign(MA_NACT, 0); r.act_distinct.assign(MA_NACT, 0);
-    r.kernels = {{"memb_expand", 0, 0, 0}, {"memb_fingerprint", 0, 0, 0}, {"memb_dedup", 0, 0, 0},
-                 {"memb_select", 0, 0, 0}, {"memb_compact", 0, 0, 0}, {"memb_materialize", 0, 0, 0}};
-    const MembRuntime& rt = rt_host_;
-    store_.reset();
-    u64 level_begin = 0, level_count = 1;
-    u32 level = 0;
-    // continue mode: the BFS kernels get a runtime without invariants, the witness
-    // kernels (memb_witness.hip) the cfg positions still pending; wits in discovery order
-    MembRuntime rt_bfs = rt_dev_;
+    for (const char* k : kernels) r.kernels.push_back({k, 0, 0, 0});
+    return r;
+  }
+  // the runtime switches of a run, on both runtime descriptors (after prepare_prefixes, which resets them)
+  void apply_run_switches(const RunOpts& o) {
+    rt_host_.sym_tlc = rt_dev_.sym_tlc = (o.sym_tlc && m_.rt.symmetry) ? 1u : 0u;
+    fp_slice_test_ = o.test_fp_slice;
+    rt_host_.disjunct_copies = rt_dev_.disjunct_copies = o.disjunct_copies ? 1u : 0u;
+  }
+  int clear_table(std::string& err) {
+    HIPCHK(hipMemsetAsync(d_table_, 0, (table_mask_ + 1) * 16, stream_));
+    HIPCHK(hipStreamSynchronize(stream_));
+    return 0;
+  }
+
+  // continue mode: the cfg positions still without a witness, the witnesses in discovery order
+  struct Continue {
     u32 pending = 0;
     std::vector<Witness> wits;
-    RunResult last_wit;                   // the result as of the last witness's stop point
-    if (cont) {
-      rt_bfs.n_inv = 0;
-      pending = rt.n_inv >= 32 ? ~0u : (1u << rt.n_inv) - 1u;
-      r.continued = true;
-      r.kernels.push_back({"memb_witness", 0, 0, 0});
-      if (!d_wit_) HIPCHK(hipMalloc(&d_wit_, WIT_N * 8));
-      for (auto& e : ev_w_) if (!e) HIPCHK(hipEventCreate(&e));
-    }
-    auto add_witness = [&](const RunResult& at, u32 q) {
+    RunResult last;                       // the result as of the last witness's stop point
+    void add_witness(const RunResult& at, u32 q, const char* invariant) {
       Witness w;
-      w.invariant = kMembInvNames[inv_id_at(q)]; w.position = (int)q;
+      w.invariant = invariant; w.position = (int)q;
       w.depth = at.depth; w.generated = at.generated; w.distinct = at.distinct; w.left_on_queue = at.left_on_queue;
       w.act_generated = at.act_generated; w.act_distinct = at.act_distinct; w.trace = at.trace;
       wits.push_back(std::move(w));
       pending &= ~(1u << q);
-    };
+    }
     // the end of a continue run that has witnesses and no fatal event: the first witness is the
     // run's counterexample (what the plain run reports)
-    auto finish_continue = [&]() {
-      if (cont && !wits.empty() && (r.verdict == MC_VERDICT_OK || r.verdict == MC_VERDICT_DEPTH_LIMIT)) {
+    void finish_continue(RunResult& r) {
+      if (!wits.empty() && (r.verdict == MC_VERDICT_OK || r.verdict == MC_VERDICT_DEPTH_LIMIT)) {
         r.verdict = MC_VERDICT_INVARIANT_VIOLATION;
         r.violated = wits[0].invariant;
         r.trace = wits[0].trace;
       }
       r.witnesses = std::move(wits);
-    };
+    }
+  };
 
-    if (!o.recover_path.empty()) {   // TLC -recover: continue the BFS saved by a checkpoint
-      if (int rc = load_checkpoint(o.recover_path, r, level_begin, level_count, err)) return rc;
-      level = (u32)(r.depth - 1);
-    } else {
-    // ---- Init (raft.tla:388-393): generated 1; constraints; invariants (TLC checks them on initial states)
+  // Init (raft.tla:388-393): generated 1; constraints; invariants (TLC checks them on initial states).
+  // Every rank evaluates it; rank 0 stores it, its fingerprint's owner seeds its seen-set (run(): rank 0 of 1).
+  // cn: continue mode, where a violation is a witness of depth 1 and the search goes on.
+  // ended: the search is over; init_text: Init's text where the verdict is about it (the caller's trace head)
+  int seed_init(RunResult& r, int rank, int world, Continue* cn, bool& ended, std::string& init_text, std::string& err) {
+    const MembRuntime& rt = rt_host_;
     W s0; S::init(s0);
     r.generated = 1; r.depth = 1;
     r.levels.push_back({1, 0, 0.0});
     store_.set_total(0);
-    if (!S::in_model(s0, s0, rt)) { r.distinct = 0; r.depth = 0; finish(r, t0); return 0; }
-    {
+    ended = true;
+    if (!S::in_model(s0, s0, rt)) { r.distinct = 0; r.depth = 0; return 0; }
+    const u64 fp0 = S::fingerprint(s0, r.seed, rt);
+    if (fp_owner(fp0, (u32)world) == (u32)rank) {
+      const u64 e2[2] = {fp0, ~0ull};   // level 0, key 0: the stored side value is ~(0 << 40 | 0)
+      HIPCHK(hipMemcpy(d_table_ + 2 * (fp0 & table_mask_), e2, 16, hipMemcpyHostToDevice));
+    }
+    if (rank == 0) {
       u32 w0[S::NW]; S::pack(s0, w0);
       u32 wp[NWP] = {0}; for (int q = 0; q < S::NW; ++q) wp[q] = w0[q];
-      const u64 fp0 = S::fingerprint(s0, r.seed, rt);
-      u64 e2[2] = {fp0, ~0ull};   // level 0, key 0: the stored side value is ~(0 << 40 | 0)
-      HIPCHK(hipMemcpy(d_table_ + 2 * (fp0 & table_mask_), e2, 16, hipMemcpyHostToDevice));
       HIPCHK(hipMemcpy(store_.states(), wp, NWP * 4, hipMemcpyHostToDevice));
       const u64 nometa = ~0ull;
       HIPCHK(hipMemcpy(store_.meta(), &nometa, 8, hipMemcpyHostToDevice));
-      store_.set_total(1); r.distinct = 1;
-      if (cont) {   // every pending invariant on Init: a violation is a witness of depth 1, the search goes on
-        for (u32 q = 0; q < rt.n_inv; ++q) {
-          const int iv = S::inv(s0, inv_id_at(q), rt);
-          if (iv == IV_ERR) {
-            r.verdict = MC_VERDICT_EVAL_ERROR; r.error = std::string("TLC evaluation error in invariant ") + kMembInvNames[inv_id_at(q)];
-            r.trace.push_back({"<Initial predicate>", text_.text(s0, true)});
-            finish_continue(); finish(r, t0); return 0;
-          }
-          if (iv == IV_BAD) {
-            RunResult at = r;
-            at.trace.push_back({"<Initial predicate>", text_.text(s0, true)});
-            add_witness(at, q);
-          }
-        }
-        if (!wits.empty() && !pending) { finish_continue(); finish(r, t0); return 0; }
-      } else if (u32 bad = S::check_invariants(s0, rt)) {
-        if ((bad >> 8) == IV_BAD) { r.verdict = MC_VERDICT_INVARIANT_VIOLATION; r.violated = kMembInvNames[bad & 255]; }
-        else { r.verdict = MC_VERDICT_EVAL_ERROR; r.error = std::string("TLC evaluation error in invariant ") + kMembInvNames[bad & 255]; }
-        r.trace.push_back({"<Initial predicate>", text_.text(s0, true)});
-        finish(r, t0); return 0;
-      }
+      store_.set_total(1);
     }
-    }
-
-    const u64 S_B = NWP * 4;
-    while (level_count > 0) {
-      if (o.max_depth && r.depth >= o.max_depth) { r.left_on_queue = (int64_t)level_count; r.verdict = MC_VERDICT_DEPTH_LIMIT; break; }
-      // the device keeps what the search still reads (the frontier) and writes (the next level);
-      // when the next level, predicted from the last growth ratio with a 1.5x margin, might not
-      // fit behind what is stored, the completed levels move to host memory
-      if (level_begin > store_.base()) {
-        const double prev = r.levels.size() >= 2 ? (double)r.levels[r.levels.size() - 2].states : 1.0;
-        const double pred = (double)level_count * std::max(1.0, (double)level_count / std::max(prev, 1.0)) * 1.5;
-        if ((double)(store_.total() - store_.base()) + pred > (double)store_.cap())
-          if (int rc = store_.spill(level_begin, level_count, stream_, false, err)) return rc;
-      }
-      // kernels index the store by global id: the device part holds [base, base + cap)
-      u32* const sp = store_.states() - store_.base() * NWP;
-      u64* const mp = store_.meta() - store_.base();
-      const u64 cap_end = store_.base() + store_.cap();
-      HIPCHK(hipMemsetAsync(d_ctr_, 0, C_NCTR * 8, stream_));
-      HIPCHK(hipMemsetAsync(d_ctr_ + C_EVENT, 0xFF, 8, stream_));
-      u64 next_write = level_begin + level_count;
-      double level_ms = 0;
-      int64_t gen_before_chunk = 0;       // generated in earlier chunks of this level
-      std::vector<u64> act_before_chunk(2 * MA_NACT, 0);   // per-action generated / distinct in earlier chunks
-      u64 gen_in_level = 0;               // in-model successors of this level (G_in)
-      u64 gin_seen = 0;                   // ... counted up to the previous chunk
-      u64 c[C_NCTR] = {0};
-      bool stop = false;
-      for (u64 cb = level_begin; cb < level_begin + level_count; cb += chunk_) {
-        const u64 cnt = std::min<u64>(chunk_, level_begin + level_count - cb), rank0 = cb - level_begin;
-        const u64 nslots = cnt * (u64)S::NSLOT;
-        const u32 nblk = (u32)((cnt + BS - 1) / BS);
-        MGenArgs g;
-        g.states = sp; g.chunk_begin = cb; g.chunk_count = cnt; g.rank0 = rank0; g.cand = d_cand_; g.cells = d_cells_;
-        g.cells_oom = d_cells_oom_; g.cell_count = d_cell_count_; g.nsucc = d_nsucc_;
-        g.seed = r.seed; g.rt = rt_bfs; g.inv_oom = o.inv_out_of_model ? 1u : 0u; g.deadlock = o.check_deadlock ? 1u : 0u; g.ctr = (unsigned long long*)d_ctr_;
-        g.smask = d_smask_;
-        MDedupArgs d;
-        d.cells = d_cells_; d.cell_count = d_cell_count_;
-        d.cand = d_cand_; d.nslots = nslots; d.chunk_count = cnt; d.rank0 = rank0; d.nslot = S::NSLOT; d.level = level + 1;
-        d.table = d_table_; d.table_mask = table_mask_; d.ctr = (unsigned long long*)d_ctr_;
-        MSelArgs sa;
-        sa.smask = d_smask_; sa.smw = (u32)SMW;
-        sa.cand = d_cand_; sa.chunk_count = cnt; sa.rank0 = rank0; sa.nslot = S::NSLOT; sa.level = level + 1; sa.table = d_table_;
-        sa.woff = d_woff_; sa.bsum = (unsigned long long*)d_bsum_;
-        MCompArgs ca;
-        ca.smask = d_smask_; ca.smw = (u32)SMW;
-        ca.cand = d_cand_; ca.chunk_count = cnt; ca.chunk_begin = cb; ca.nslot = S::NSLOT; ca.woff = d_woff_;
-        ca.bsum = (const unsigned long long*)d_bsum_; ca.newrec = d_newrec_;
-        HIPCHK(hipEventRecord(ev_[7], stream_));
-        hipLaunchKernelGGL((memb_expand<S>), dim3(nblk), dim3(BS), 0, stream_, g);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(ev_[8], stream_));
-        // (continue mode: memb_witness_oom takes this launch's place, after memb_materialize)
-        if (o.inv_out_of_model && !cont) hipLaunchKernelGGL((memb_oom_check<S>), dim3(nblk), dim3(BS), 0, stream_, g);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(ev_[0], stream_));
-        if (int rc = launch_fingerprint(g, nblk, err)) return rc;
-        HIPCHK(hipEventRecord(ev_[1], stream_));
-        hipLaunchKernelGGL(memb_dedup_cells, dim3(nblk), dim3(BS), 0, stream_, d);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(ev_[2], stream_));
-        hipLaunchKernelGGL(memb_select, dim3(nblk), dim3(BS), 0, stream_, sa);
-        HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(memb_scan_blocks, dim3(1), dim3(BS), 0, stream_, (unsigned long long*)d_bsum_, nblk, (unsigned long long*)d_ctr_);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(ev_[3], stream_));
-        hipLaunchKernelGGL(memb_compact, dim3(nblk), dim3(BS), 0, stream_, ca);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(ev_[4], stream_));
-        u64 nnew = 0;
-        HIPCHK(hipMemcpyAsync(&nnew, d_ctr_ + C_NEW, 8, hipMemcpyDeviceToHost, stream_));
-        HIPCHK(hipStreamSynchronize(stream_));
-        const float ms_x = ms(7, 8), ms_g = ms(0, 1), ms_d = ms(1, 2), ms_s = ms(2, 3), ms_c = ms(3, 4);
-
-        float ms_m = 0;
-        if (nnew && next_write + nnew <= cap_end) {
-          MMatArgs m;
-          m.states = sp; m.meta = mp; m.newrec = d_newrec_; m.n_new = nnew; m.dst_base = next_write; m.cap = cap_end;
-          m.level_begin = level_begin; m.gid_tag = 0; m.rt = rt_bfs; m.ctr = (unsigned long long*)d_ctr_;
-          HIPCHK(hipEventRecord(ev_[5], stream_));
-          if (rt_dev_.sym_tlc) hipLaunchKernelGGL((memb_materialize<S, true>), dim3((unsigned)((nnew + BS - 1) / BS)), dim3(BS), 0, stream_, m);
-          else hipLaunchKernelGGL((memb_materialize<S, false>), dim3((unsigned)((nnew + BS - 1) / BS)), dim3(BS), 0, stream_, m);
-          HIPCHK(hipGetLastError());
-          HIPCHK(hipEventRecord(ev_[6], stream_));
-          HIPCHK(hipEventSynchronize(ev_[6]));
-          ms_m = ms(5, 6);
+    r.distinct = 1;
+    if (cn) {   // every pending invariant on Init
+      for (u32 q = 0; q < rt.n_inv; ++q) {
+        const int iv = S::inv(s0, inv_id_at(q), rt);
+        if (iv == IV_ERR) {
+          r.verdict = MC_VERDICT_EVAL_ERROR; r.error = std::string("TLC evaluation error in invariant ") + kMembInvNames[inv_id_at(q)];
+          init_text = text_.text(s0, true);
+          return 0;
         }
-        HIPCHK(hipMemcpyAsync(c, d_ctr_, sizeof c, hipMemcpyDeviceToHost, stream_));
-        HIPCHK(hipStreamSynchronize(stream_));
-        level_ms += ms_x + ms_g + ms_d + ms_s + ms_c + ms_m;
-        const u64 ncells = c[C_GEN_IN] - gin_seen;        // in-model successors of this chunk
-        gin_seen = c[C_GEN_IN];
-        r.kernels[0].ms += ms_x; r.kernels[0].launches++; r.kernels[0].algo_bytes += (double)cnt * S_B + (double)nslots * 8 + (double)ncells * 4;
-        r.kernels[1].ms += ms_g; r.kernels[1].launches++; r.kernels[1].algo_bytes += (double)ncells * (4 + S_B + 8);
-        r.kernels[2].ms += ms_d; r.kernels[2].launches++; r.kernels[2].algo_bytes += (double)nslots * 16 + (double)ncells * 16;
-        r.kernels[3].ms += ms_s; r.kernels[3].launches++; r.kernels[3].algo_bytes += (double)nslots * 8 + (double)ncells * 16 + (double)cnt * 4;
-        r.kernels[4].ms += ms_c; r.kernels[4].launches++; r.kernels[4].algo_bytes += (double)nslots * 8 + (double)nnew * 8;
-        if (ms_m > 0) { r.kernels[5].ms += ms_m; r.kernels[5].launches++; r.kernels[5].algo_bytes += (double)nnew * (8 + 2 * S_B + 8); }
-        if (next_write + nnew > cap_end) { c[C_ERR] |= MERR_STORE; stop = true; }
+        if (iv == IV_BAD) {
+          RunResult at = r;
+          at.trace.push_back({"<Initial predicate>", text_.text(s0, true)});
+          cn->add_witness(at, q, kMembInvNames[inv_id_at(q)]);
+        }
+      }
+      ended = !cn->wits.empty() && !cn->pending;
+    } else if (u32 bad = S::check_invariants(s0, rt)) {
+      if ((bad >> 8) == IV_BAD) { r.verdict = MC_VERDICT_INVARIANT_VIOLATION; r.violated = kMembInvNames[bad & 255]; }
+      else { r.verdict = MC_VERDICT_EVAL_ERROR; r.error = std::string("TLC evaluation error in invariant ") + kMembInvNames[bad & 255]; }
+      init_text = text_.text(s0, true);
+    } else {
+      ended = false;
+    }
+    return 0;
+  }
+
+  // ================================================================ the pipeline stages
+  // One args builder and one launcher per stage, used by the single-GPU level loop (run) and by the
+  // sharded step API (shard_generate .. shard_materialize; the native loop drives the same steps).
+  // Each stage sits in an event pair of its own from one pool that grows on demand
+  // (DevOwner::pool_event): timed_begin / timed_end queue it, harvest() reads the pairs back after
+  // the caller's next host synchronisation.
+  hipEvent_t pool_ev(size_t i) { return (hipEvent_t)res_.pool_event(i); }
+  int timed_begin(RunResult& r, int k, int launches, std::string& err) {
+    hipEvent_t const e0 = pool_ev(2 * pending_.size()), e1 = pool_ev(2 * pending_.size() + 1);
+    if (!e0 || !e1) { err = "hipEventCreate failed"; return MC_E_NO_DEVICE; }
+    HIPCHK(hipEventRecord(e0, stream_));
+    pending_.push_back(k);
+    r.kernels[k].launches += launches;
+    return 0;
+  }
+  int timed_end(std::string& err, bool wait = false) {   // wait: the host waits for the stage
+    hipEvent_t const e1 = pool_ev(2 * pending_.size() - 1);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(e1, stream_));
+    if (wait) HIPCHK(hipEventSynchronize(e1));
+    return 0;
+  }
+  template <class F>
+  int timed(RunResult& r, int k, F&& launch, std::string& err) {
+    if (int rc = timed_begin(r, k, 1, err)) return rc;
+    launch();
+    return timed_end(err);
+  }
+  // every queued pair's milliseconds to its kernel; their sum (the level's kernel time grows by it)
+  double harvest(RunResult& r) {
+    double sum = 0;
+    for (size_t i = 0; i < pending_.size(); ++i) {
+      float ms = 0;
+      (void)hipEventElapsedTime(&ms, pool_ev(2 * i), pool_ev(2 * i + 1));
+      r.kernels[pending_[i]].ms += ms;
+      sum += ms;
+    }
+    pending_.clear();
+    return sum;
+  }
+
+  // the chunk [chunk_begin, chunk_begin + count) of a level, its first state of rank rank0; states: the
+  // store indexed as chunk_begin is; smask: the single-GPU loop's slot masks, null for the dense cand
+  // form (memb_route / memb_dedup_sh / memb_select_sh read every slot)
+  MGenArgs gen_args(const u32* states, u64 chunk_begin, u64 count, u64 rank0, u64 seed, const MembRuntime& rt, const RunOpts& o,
+                    u64* smask) const {
+    MGenArgs g{};
+    g.states = states; g.chunk_begin = chunk_begin; g.chunk_count = count; g.rank0 = rank0; g.cand = d_cand_; g.cells = d_cells_;
+    g.cells_oom = d_cells_oom_; g.cell_count = d_cell_count_; g.nsucc = d_nsucc_;
+    g.seed = seed; g.rt = rt; g.inv_oom = o.inv_out_of_model ? 1u : 0u; g.deadlock = o.check_deadlock ? 1u : 0u;
+    g.ctr = (unsigned long long*)d_ctr_;
+    g.smask = smask;
+    return g;
+  }
+  // phase 1 (kernel 0 of r): memb_expand and, with_oom, memb_oom_check behind it.  The event pair closes
+  // behind memb_expand on the single-GPU path and behind memb_oom_check on the sharded one, as each
+  // path has always timed it.
+  int launch_expand(const MGenArgs& g, u32 nblk, bool with_oom, RunResult& r, std::string& err) {
+    if (int rc = timed_begin(r, 0, 1, err)) return rc;
+    hipLaunchKernelGGL((memb_expand<S>), dim3(nblk), dim3(BS), 0, stream_, g);
+    if (sharded_) HIPCHK(hipGetLastError());
+    else if (int rc = timed_end(err)) return rc;
+    if (with_oom) hipLaunchKernelGGL((memb_oom_check<S>), dim3(nblk), dim3(BS), 0, stream_, g);
+    if (sharded_) return timed_end(err);
+    HIPCHK(hipGetLastError());
+    return 0;
+  }
+  // phase 6: n_new winners' records at newrec, re-derived behind dst_base of a store of cap slots;
+  // level_begin: gid - level_begin = rank in the level; gid_tag: or-ed into the parent pointers
+  MMatArgs mat_args(u32* states, u64* meta, const u64* newrec, u64 n_new, u64 dst_base, u64 cap, u64 level_begin, u64 gid_tag,
+                    const MembRuntime& rt) const {
+    MMatArgs m;
+    m.states = states; m.meta = meta; m.newrec = newrec; m.n_new = n_new; m.dst_base = dst_base; m.cap = cap;
+    m.level_begin = level_begin; m.gid_tag = gid_tag; m.rt = rt; m.ctr = (unsigned long long*)d_ctr_;
+    return m;
+  }
+  void launch_materialize(const MMatArgs& m) {
+    const dim3 grid((unsigned)((m.n_new + BS - 1) / BS));
+    if (rt_dev_.sym_tlc) hipLaunchKernelGGL((memb_materialize<S, true>), grid, dim3(BS), 0, stream_, m);
+    else hipLaunchKernelGGL((memb_materialize<S, false>), grid, dim3(BS), 0, stream_, m);
+  }
+
+  // ================================================================ the single-GPU search
+  // One run's state, shared by run()'s level loop and its steps below.
+  struct Search {
+    std::chrono::steady_clock::time_point t0;
+    bool cont = false;              // continue mode
+    MembRuntime rt_bfs;             // what the BFS kernels get: rt_dev_, in continue mode without its invariants
+    u64 level_begin = 0, level_count = 1;
+    u32 level = 0;
+    // the level being expanded: the store rebased to global ids and its end, where the next new state
+    // goes, and what the chunks read back so far
+    u32* sp = nullptr; u64* mp = nullptr;
+    u64 cap_end = 0, next_write = 0;
+    double level_ms = 0;
+    int64_t gen_before_chunk = 0;        // generated in earlier chunks of this level
+    std::vector<u64> act_before_chunk;   // per-action generated / distinct in earlier chunks
+    u64 gin_seen = 0;                    // in-model successors counted up to the previous chunk
+    u64 c[C_NCTR] = {0};                 // the level's counters as of the last chunk
+    bool stop = false;
+    // the chunk in flight
+    u64 cb = 0, cnt = 0, rank0 = 0, nnew = 0;
+    u32 nblk = 0;
+    MGenArgs g;
+    bool stored = false;                 // memb_materialize ran: the chunk's new states are in the store
+    u64 level_end() const { return level_begin + level_count; }
+  };
+
+  // Set up, then per level: spill?, then per chunk of the frontier queue its kernels, read it back,
+  // find its witnesses (continue mode) and its first event; commit the level.
+  int run(const RunOpts& o, RunResult& r, std::string& err) override {
+    Search s;
+    Continue cn;
+    if (int rc = begin_search(o, s, cn, r, err)) return rc;
+    if (!o.recover_path.empty()) {   // TLC -recover: continue the BFS saved by a checkpoint
+      if (int rc = load_checkpoint(o.recover_path, r, s.level_begin, s.level_count, err)) return rc;
+      s.level = (u32)(r.depth - 1);
+    } else {
+      bool ended = false;
+      std::string init_text;
+      if (int rc = seed_init(r, 0, 1, s.cont ? &cn : nullptr, ended, init_text, err)) return rc;
+      if (!init_text.empty()) r.trace.push_back({"<Initial predicate>", init_text});
+      if (ended) return end_run(s, cn, r);
+    }
+    while (s.level_count > 0) {
+      if (o.max_depth && r.depth >= o.max_depth) { r.left_on_queue = (int64_t)s.level_count; r.verdict = MC_VERDICT_DEPTH_LIMIT; break; }
+      if (int rc = maybe_spill(s, r, err)) return rc;
+      if (int rc = begin_level(s, err)) return rc;
+      for (u64 cb = s.level_begin; cb < s.level_end() && !s.stop; cb += chunk_) {
+        if (int rc = queue_chunk(o, s, r, cb, err)) return rc;
+        if (int rc = read_chunk(s, r, err)) return rc;
         u32 fatal_pending = 0;
-        if (cont && !c[C_ERR]) {
-          // This chunk's witnesses: per pending position the minimum violating key, unless a fatal event
-          // (an invariant that failed to evaluate, a next-state error, a deadlock) comes first in key
-          // order.  The kernels evaluate a position on the whole chunk, the rules retire it at its
-          // witness: when an invariant's error is the fatal event and positions were retired before
-          // it, the pass runs again without them (the error may have been one of theirs).
-          const bool wnew = nnew && next_write + nnew <= cap_end;   // (memb_materialize ran: the chunk's new states are stored)
-          std::vector<std::pair<u64, u32>> hits;
-          u32 mask = pending;
-          u64 fatal = c[C_EVENT];
-          while (mask && (o.inv_out_of_model || wnew)) {
-            MWitArgs wa;
-            wa.states = sp; wa.meta = mp; wa.first = next_write; wa.n_new = nnew; wa.level_begin = level_begin; wa.rt = rt_dev_;
-            wa.pending = mask; wa.wit = (unsigned long long*)d_wit_;
-            u64 wit[WIT_N];
-            HIPCHK(hipMemsetAsync(d_wit_, 0xFF, WIT_N * 8, stream_));
-            HIPCHK(hipEventRecord(ev_w_[0], stream_));
-            if (o.inv_out_of_model) hipLaunchKernelGGL((memb_witness_oom<S>), dim3(nblk), dim3(BS), 0, stream_, g, wa);
-            HIPCHK(hipGetLastError());
-            if (wnew) hipLaunchKernelGGL((memb_witness_new<S>), dim3((unsigned)((nnew + BS - 1) / BS)), dim3(BS), 0, stream_, wa);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipEventRecord(ev_w_[1], stream_));
-            HIPCHK(hipMemcpyAsync(wit, d_wit_, sizeof wit, hipMemcpyDeviceToHost, stream_));
-            HIPCHK(hipStreamSynchronize(stream_));
-            float ms_w = 0;
-            (void)hipEventElapsedTime(&ms_w, ev_w_[0], ev_w_[1]);
-            level_ms += ms_w;
-            auto& kw = r.kernels.back();
-            kw.ms += ms_w; kw.launches += (o.inv_out_of_model ? 1 : 0) + (wnew ? 1 : 0);
-            kw.algo_bytes += (double)(wnew ? nnew : 0) * (8 + S::BAGW * 4);
-            fatal = std::min(c[C_EVENT], wit[WIT_FATAL]);
-            u32 found = 0;
-            for (u32 q = 0; q < 32; ++q)
-              if (((mask >> q) & 1u) && wit[q] != ~0ull && ((wit[q] << 2) | EV_VIOLATION) < fatal) { hits.push_back({wit[q], q}); found |= 1u << q; }
-            mask &= ~found;
-            if (!(found && wit[WIT_FATAL] != ~0ull && wit[WIT_FATAL] <= c[C_EVENT])) break;
-            fatal = c[C_EVENT];   // (what holds if the next pass finds no error)
-          }
-          std::sort(hits.begin(), hits.end());
-          fatal_pending = mask;   // an erroring invariant is named among the positions pending at its key
-          // each witness gets TLC's stop point as if the search had ended on it, on a copy of the result
-          for (const auto& h : hits) {
-            u64 c2[C_NCTR];
-            std::memcpy(c2, c, sizeof c2);
-            c2[C_EVENT] = (h.first << 2) | EV_VIOLATION;
-            RunResult at = r;
-            if (int rc = handle_event(c2, cnt, level_begin, level_count, rank0, gen_before_chunk, next_write - (level_begin + level_count), nnew, level,
-                                      at, err, (int)h.second)) return rc;
-            stop_action_counts(c2, sp, mp, cb, level_begin, rank0, next_write, act_before_chunk, at);
-            add_witness(at, h.second);
-            last_wit = std::move(at);
-          }
-          c[C_EVENT] = fatal;
-          if (fatal == ~0ull && !pending && !hits.empty()) {
-            // every listed invariant has its witness: the run ends at the last one's stop point
-            r.generated = last_wit.generated; r.distinct = last_wit.distinct; r.left_on_queue = last_wit.left_on_queue;
-            r.depth = last_wit.depth; r.act_generated = last_wit.act_generated; r.act_distinct = last_wit.act_distinct;
-            r.verdict = MC_VERDICT_INVARIANT_VIOLATION;
-            stop = true;
-          }
-        }
-        if (c[C_EVENT] != ~0ull) {
+        if (s.cont && !s.c[C_ERR])
+          if (int rc = witness_pass(o, s, cn, r, fatal_pending, err)) return rc;
+        if (s.c[C_EVENT] != ~0ull) {
           // first event of this chunk in key order (earlier chunks had none)
-          if (int rc = handle_event(c, cnt, level_begin, level_count, rank0, gen_before_chunk, next_write - (level_begin + level_count), nnew, level,
-                                    r, err, -1, fatal_pending)) return rc;
-          stop_action_counts(c, sp, mp, cb, level_begin, rank0, next_write, act_before_chunk, r);
-          stop = true;
+          if (int rc = handle_event(s.c, s.cnt, s.level_begin, s.level_count, s.rank0, s.gen_before_chunk, s.next_write - s.level_end(), s.nnew,
+                                    s.level, r, err, -1, fatal_pending)) return rc;
+          stop_action_counts(s.c, s.sp, s.mp, s.cb, s.level_begin, s.rank0, s.next_write, s.act_before_chunk, r);
+          s.stop = true;
         }
-        if (c[C_ERR]) stop = true;
-        if (stop) break;
-        next_write += nnew;
-        int64_t g_all = 0; for (int k = 0; k < MA_NACT; ++k) g_all += (int64_t)c[C_ACT + k];
-        gen_before_chunk = g_all;
-        for (int k = 0; k < 2 * MA_NACT; ++k) act_before_chunk[k] = c[C_ACT + k];
+        if (s.c[C_ERR]) s.stop = true;
+        if (s.stop) break;
+        s.next_write += s.nnew;
+        s.gen_before_chunk = 0;
+        for (int k = 0; k < MA_NACT; ++k) s.gen_before_chunk += (int64_t)s.c[C_ACT + k];
+        for (int k = 0; k < 2 * MA_NACT; ++k) s.act_before_chunk[k] = s.c[C_ACT + k];
       }
-      r.seconds_kernels += level_ms / 1000.0;
+      r.seconds_kernels += s.level_ms / 1000.0;
       r.n_launches += 1;
-      if (c[C_ERR] && r.verdict == MC_VERDICT_OK) {
-        const u64 e = c[C_ERR];
+      if (s.c[C_ERR] && r.verdict == MC_VERDICT_OK) {
         r.verdict = MC_VERDICT_CAPACITY_OVERFLOW;
-        std::ostringstream os;
-        os << "error flags 0x" << std::hex << e << std::dec << ":";
-        if (e & ME_CAP) os << " a field, message count or the message bag exceeded its compiled capacity (state "
-                           << (c[C_ERRGID] ? (int64_t)c[C_ERRGID] - 1 : -1) << ");";
-        if (e & MERR_STORE) os << " state store full (raise state_store_bytes);";
-        if (e & MERR_TABLE_FULL) os << " fingerprint table full (raise fp_table_bytes);";
-        r.error = os.str();
+        r.error = capacity_error(s.c);
       }
-      if (stop) {
+      if (s.stop) {
         if (r.verdict == MC_VERDICT_OK) r.verdict = MC_VERDICT_CAPACITY_OVERFLOW;
-        if (r.verdict == MC_VERDICT_INVARIANT_VIOLATION && cont) { r.violated = wits[0].invariant; r.trace = wits[0].trace; }
+        if (r.verdict == MC_VERDICT_INVARIANT_VIOLATION && s.cont) { r.violated = cn.wits[0].invariant; r.trace = cn.wits[0].trace; }
         break;
       }
-      int64_t gen = 0;
-      for (int k = 0; k < MA_NACT; ++k) { r.act_generated[k] += (int64_t)c[C_ACT + k]; r.act_distinct[k] += (int64_t)c[C_ACT + MA_NACT + k]; gen += (int64_t)c[C_ACT + k]; }
-      r.generated += gen;
-      gen_in_level = c[C_GEN_IN];
-      r.generated_in_model += (int64_t)gen_in_level;
-      const u64 nnew = next_write - (level_begin + level_count);
-      r.algo_bytes += (double)level_count * S_B + (double)gen_in_level * 8 + (double)nnew * (16 + S_B);
-      store_.set_total(next_write);
-      r.distinct = (int64_t)next_write;
-      r.levels.back().generated = gen;
-      r.levels.back().kernel_ms = level_ms;
-      if (nnew > 0) { r.levels.push_back({(int64_t)nnew, 0, 0.0}); r.depth += 1; }
-      level_begin += level_count;
-      level_count = nnew;
-      ++level;
-      if (o.checkpoint_every > 0 && !o.checkpoint_path.empty() && r.depth % o.checkpoint_every == 0 && level_count > 0)
-        if (int rc = save_checkpoint(o.checkpoint_path, r, level_begin, level_count, err)) return rc;
+      commit_level(s, r);
+      if (o.checkpoint_every > 0 && !o.checkpoint_path.empty() && r.depth % o.checkpoint_every == 0 && s.level_count > 0)
+        if (int rc = save_checkpoint(o.checkpoint_path, r, s.level_begin, s.level_count, err)) return rc;
     }
-    finish_continue();
-    finish(r, t0);
+    return end_run(s, cn, r);
+  }
+  int end_run(const Search& s, Continue& cn, RunResult& r) {
+    cn.finish_continue(r);
+    finish(r, s.t0);
     return 0;
+  }
+
+  // option refusals, allocations, prefixes and runtime switches, an empty seen-set and the result header
+  int begin_search(const RunOpts& o, Search& s, Continue& cn, RunResult& r, std::string& err) {
+    sharded_ = false;
+    s.cont = o.continue_mode;
+    if (s.cont && (!o.checkpoint_path.empty() || !o.recover_path.empty() || o.sim_walks > 0)) {
+      err = "continue mode: not with a checkpoint or recover path, nor with simulation";
+      return MC_E_UNSUPPORTED;
+    }
+    if (int rc = require_prefixes(err, kPrefixHint)) return rc;
+    if (int rc = ensure_alloc(o, err)) return rc;
+    if (int rc = prepare_prefixes(err)) return rc;
+    apply_run_switches(o);
+    s.t0 = std::chrono::steady_clock::now();
+    if (int rc = clear_table(err)) return rc;
+    r = new_result(o.seed, {"memb_expand", "memb_fingerprint", "memb_dedup", "memb_select", "memb_compact", "memb_materialize"});
+    store_.reset();
+    pending_.clear();
+    // continue mode: the BFS kernels get a runtime without invariants, the witness kernels
+    // (memb_witness.hip) the cfg positions still pending
+    s.rt_bfs = rt_dev_;
+    if (s.cont) {
+      s.rt_bfs.n_inv = 0;
+      cn.pending = rt_host_.n_inv >= 32 ? ~0u : (1u << rt_host_.n_inv) - 1u;
+      r.continued = true;
+      r.kernels.push_back({"memb_witness", 0, 0, 0});
+      if (!d_wit_) HIPCHK(res_.device(&d_wit_, WIT_N * 8));
+    }
+    return 0;
+  }
+
+  // the device keeps what the search still reads (the frontier) and writes (the next level);
+  // when the next level, predicted from the last growth ratio with a 1.5x margin, might not
+  // fit behind what is stored, the completed levels move to host memory
+  int maybe_spill(const Search& s, const RunResult& r, std::string& err) {
+    if (s.level_begin <= store_.base()) return 0;
+    const double prev = r.levels.size() >= 2 ? (double)r.levels[r.levels.size() - 2].states : 1.0;
+    const double pred = (double)s.level_count * std::max(1.0, (double)s.level_count / std::max(prev, 1.0)) * 1.5;
+    if ((double)(store_.total() - store_.base()) + pred <= (double)store_.cap()) return 0;
+    return store_.spill(s.level_begin, s.level_count, stream_, false, err);
+  }
+
+  int begin_level(Search& s, std::string& err) {
+    // kernels index the store by global id: the device part holds [base, base + cap)
+    s.sp = store_.states() - store_.base() * NWP;
+    s.mp = store_.meta() - store_.base();
+    s.cap_end = store_.base() + store_.cap();
+    HIPCHK(hipMemsetAsync(d_ctr_, 0, C_NCTR * 8, stream_));
+    HIPCHK(hipMemsetAsync(d_ctr_ + C_EVENT, 0xFF, 8, stream_));
+    s.next_write = s.level_end();
+    s.level_ms = 0;
+    s.gen_before_chunk = 0;
+    s.act_before_chunk.assign(2 * MA_NACT, 0);
+    s.gin_seen = 0;
+    std::memset(s.c, 0, sizeof s.c);
+    s.stop = false;
+    return 0;
+  }
+
+  // phases 1 to 5 of the chunk at cb on the stream; no host wait
+  int queue_chunk(const RunOpts& o, Search& s, RunResult& r, u64 cb, std::string& err) {
+    s.cb = cb; s.cnt = std::min<u64>(chunk_, s.level_end() - cb); s.rank0 = cb - s.level_begin;
+    s.nblk = (u32)((s.cnt + BS - 1) / BS);
+    const u64 cnt = s.cnt, nslots = cnt * (u64)S::NSLOT;
+    const u32 nblk = s.nblk;
+    s.g = gen_args(s.sp, cb, cnt, s.rank0, r.seed, s.rt_bfs, o, d_smask_);
+    MDedupArgs d;
+    d.cells = d_cells_; d.cell_count = d_cell_count_;
+    d.cand = d_cand_; d.nslots = nslots; d.chunk_count = cnt; d.rank0 = s.rank0; d.nslot = S::NSLOT; d.level = s.level + 1;
+    d.table = d_table_; d.table_mask = table_mask_; d.ctr = (unsigned long long*)d_ctr_;
+    MSelArgs sa;
+    sa.smask = d_smask_; sa.smw = (u32)SMW;
+    sa.cand = d_cand_; sa.chunk_count = cnt; sa.rank0 = s.rank0; sa.nslot = S::NSLOT; sa.level = s.level + 1; sa.table = d_table_;
+    sa.woff = d_woff_; sa.bsum = (unsigned long long*)d_bsum_;
+    MCompArgs ca;
+    ca.smask = d_smask_; ca.smw = (u32)SMW;
+    ca.cand = d_cand_; ca.chunk_count = cnt; ca.chunk_begin = cb; ca.nslot = S::NSLOT; ca.woff = d_woff_;
+    ca.bsum = (const unsigned long long*)d_bsum_; ca.newrec = d_newrec_;
+    // (continue mode: memb_witness_oom takes memb_oom_check's place, after memb_materialize)
+    if (int rc = launch_expand(s.g, nblk, o.inv_out_of_model && !s.cont, r, err)) return rc;
+    if (int rc = timed_begin(r, 1, 1, err)) return rc;
+    if (int rc = launch_fingerprint(s.g, nblk, err)) return rc;
+    if (int rc = timed_end(err)) return rc;
+    if (int rc = timed(r, 2, [&] { hipLaunchKernelGGL(memb_dedup_cells, dim3(nblk), dim3(BS), 0, stream_, d); }, err)) return rc;
+    if (int rc = timed(r, 3, [&] {
+          hipLaunchKernelGGL(memb_select, dim3(nblk), dim3(BS), 0, stream_, sa);
+          hipLaunchKernelGGL(memb_scan_blocks, dim3(1), dim3(BS), 0, stream_, (unsigned long long*)d_bsum_, nblk, (unsigned long long*)d_ctr_);
+        }, err)) return rc;
+    return timed(r, 4, [&] { hipLaunchKernelGGL(memb_compact, dim3(nblk), dim3(BS), 0, stream_, ca); }, err);
+  }
+
+  // the chunk's two host waits: the number of winners (memb_materialize's grid), then, behind
+  // memb_materialize, the level's counters; the chunk's kernel times and byte accounting
+  int read_chunk(Search& s, RunResult& r, std::string& err) {
+    s.nnew = 0;
+    HIPCHK(hipMemcpyAsync(&s.nnew, d_ctr_ + C_NEW, 8, hipMemcpyDeviceToHost, stream_));
+    HIPCHK(hipStreamSynchronize(stream_));
+    const u64 cnt = s.cnt, nslots = cnt * (u64)S::NSLOT, nnew = s.nnew, S_B = NWP * 4;
+    s.stored = nnew && s.next_write + nnew <= s.cap_end;
+    if (s.stored) {
+      if (int rc = timed_begin(r, 5, 1, err)) return rc;
+      launch_materialize(mat_args(s.sp, s.mp, d_newrec_, nnew, s.next_write, s.cap_end, s.level_begin, 0, s.rt_bfs));
+      if (int rc = timed_end(err, true)) return rc;
+    }
+    HIPCHK(hipMemcpyAsync(s.c, d_ctr_, sizeof s.c, hipMemcpyDeviceToHost, stream_));
+    HIPCHK(hipStreamSynchronize(stream_));
+    s.level_ms += harvest(r);
+    const u64 ncells = s.c[C_GEN_IN] - s.gin_seen;        // in-model successors of this chunk
+    s.gin_seen = s.c[C_GEN_IN];
+    r.kernels[0].algo_bytes += (double)cnt * S_B + (double)nslots * 8 + (double)ncells * 4;
+    r.kernels[1].algo_bytes += (double)ncells * (4 + S_B + 8);
+    r.kernels[2].algo_bytes += (double)nslots * 16 + (double)ncells * 16;
+    r.kernels[3].algo_bytes += (double)nslots * 8 + (double)ncells * 16 + (double)cnt * 4;
+    r.kernels[4].algo_bytes += (double)nslots * 8 + (double)nnew * 8;
+    if (s.stored) r.kernels[5].algo_bytes += (double)nnew * (8 + 2 * S_B + 8);
+    if (s.next_write + nnew > s.cap_end) { s.c[C_ERR] |= MERR_STORE; s.stop = true; }
+    return 0;
+  }
+
+  // Continue mode, this chunk's witnesses: per pending position the minimum violating key, unless a fatal
+  // event (an invariant that failed to evaluate, a next-state error, a deadlock) comes first in key
+  // order.  The kernels evaluate a position on the whole chunk, the rules retire it at its
+  // witness: when an invariant's error is the fatal event and positions were retired before
+  // it, the pass runs again without them (the error may have been one of theirs).
+  // fatal_pending: an erroring invariant is named among the positions pending at its key
+  int witness_pass(const RunOpts& o, Search& s, Continue& cn, RunResult& r, u32& fatal_pending, std::string& err) {
+    u64* const c = s.c;
+    const u64 nnew = s.nnew;
+    std::vector<std::pair<u64, u32>> hits;
+    u32 mask = cn.pending;
+    u64 fatal = c[C_EVENT];
+    while (mask && (o.inv_out_of_model || s.stored)) {
+      MWitArgs wa;
+      wa.states = s.sp; wa.meta = s.mp; wa.first = s.next_write; wa.n_new = nnew; wa.level_begin = s.level_begin; wa.rt = rt_dev_;
+      wa.pending = mask; wa.wit = (unsigned long long*)d_wit_;
+      u64 wit[WIT_N];
+      HIPCHK(hipMemsetAsync(d_wit_, 0xFF, WIT_N * 8, stream_));
+      if (int rc = timed_begin(r, (int)r.kernels.size() - 1, (o.inv_out_of_model ? 1 : 0) + (s.stored ? 1 : 0), err)) return rc;
+      if (o.inv_out_of_model) hipLaunchKernelGGL((memb_witness_oom<S>), dim3(s.nblk), dim3(BS), 0, stream_, s.g, wa);
+      if (s.stored) hipLaunchKernelGGL((memb_witness_new<S>), dim3((unsigned)((nnew + BS - 1) / BS)), dim3(BS), 0, stream_, wa);
+      if (int rc = timed_end(err)) return rc;
+      HIPCHK(hipMemcpyAsync(wit, d_wit_, sizeof wit, hipMemcpyDeviceToHost, stream_));
+      HIPCHK(hipStreamSynchronize(stream_));
+      s.level_ms += harvest(r);
+      r.kernels.back().algo_bytes += (double)(s.stored ? nnew : 0) * (8 + S::BAGW * 4);
+      fatal = std::min(c[C_EVENT], wit[WIT_FATAL]);
+      u32 found = 0;
+      for (u32 q = 0; q < 32; ++q)
+        if (((mask >> q) & 1u) && wit[q] != ~0ull && ((wit[q] << 2) | EV_VIOLATION) < fatal) { hits.push_back({wit[q], q}); found |= 1u << q; }
+      mask &= ~found;
+      if (!(found && wit[WIT_FATAL] != ~0ull && wit[WIT_FATAL] <= c[C_EVENT])) break;
+      fatal = c[C_EVENT];   // (what holds if the next pass finds no error)
+    }
+    std::sort(hits.begin(), hits.end());
+    fatal_pending = mask;
+    // each witness gets TLC's stop point as if the search had ended on it, on a copy of the result
+    for (const auto& h : hits) {
+      u64 c2[C_NCTR];
+      std::memcpy(c2, c, sizeof c2);
+      c2[C_EVENT] = (h.first << 2) | EV_VIOLATION;
+      RunResult at = r;
+      if (int rc = handle_event(c2, s.cnt, s.level_begin, s.level_count, s.rank0, s.gen_before_chunk, s.next_write - s.level_end(), nnew, s.level,
+                                at, err, (int)h.second)) return rc;
+      stop_action_counts(c2, s.sp, s.mp, s.cb, s.level_begin, s.rank0, s.next_write, s.act_before_chunk, at);
+      cn.add_witness(at, h.second, kMembInvNames[inv_id_at(h.second)]);
+      cn.last = std::move(at);
+    }
+    c[C_EVENT] = fatal;
+    if (fatal == ~0ull && !cn.pending && !hits.empty()) {
+      // every listed invariant has its witness: the run ends at the last one's stop point
+      const RunResult& w = cn.last;
+      r.generated = w.generated; r.distinct = w.distinct; r.left_on_queue = w.left_on_queue;
+      r.depth = w.depth; r.act_generated = w.act_generated; r.act_distinct = w.act_distinct;
+      r.verdict = MC_VERDICT_INVARIANT_VIOLATION;
+      s.stop = true;
+    }
+    return 0;
+  }
+
+  std::string capacity_error(const u64* c) const {
+    const u64 e = c[C_ERR];
+    std::ostringstream os;
+    os << "error flags 0x" << std::hex << e << std::dec << ":";
+    if (e & ME_CAP) os << " a field, message count or the message bag exceeded its compiled capacity (state "
+                       << (c[C_ERRGID] ? (int64_t)c[C_ERRGID] - 1 : -1) << ");";
+    if (e & MERR_STORE) os << " state store full (raise state_store_bytes);";
+    if (e & MERR_TABLE_FULL) os << " fingerprint table full (raise fp_table_bytes);";
+    return os.str();
+  }
+
+  // the level is whole: its counters into the result, its new states the next frontier
+  void commit_level(Search& s, RunResult& r) {
+    const u64* const c = s.c;
+    const u64 S_B = NWP * 4;
+    int64_t gen = 0;
+    for (int k = 0; k < MA_NACT; ++k) { r.act_generated[k] += (int64_t)c[C_ACT + k]; r.act_distinct[k] += (int64_t)c[C_ACT + MA_NACT + k]; gen += (int64_t)c[C_ACT + k]; }
+    r.generated += gen;
+    const u64 gen_in_level = c[C_GEN_IN];   // in-model successors of this level (G_in)
+    r.generated_in_model += (int64_t)gen_in_level;
+    const u64 nnew = s.next_write - s.level_end();
+    r.algo_bytes += (double)s.level_count * S_B + (double)gen_in_level * 8 + (double)nnew * (16 + S_B);
+    store_.set_total(s.next_write);
+    r.distinct = (int64_t)s.next_write;
+    r.levels.back().generated = gen;
+    r.levels.back().kernel_ms = s.level_ms;
+    if (nnew > 0) { r.levels.push_back({(int64_t)nnew, 0, 0.0}); r.depth += 1; }
+    s.level_begin += s.level_count;
+    s.level_count = nnew;
+    ++s.level;
   }
 
   // ---------------------------------------------------------------- checkpoint / recover
@@ -1429,8 +1586,8 @@ class MembGpu : public Backend {
   // (none for a next-state error), and the new states before the event (key order = store order)
   int stop_counts_dev(const u32* sp, u64 first, u64 npar, u64 stop, int stop_slot, u32 kind, const u64* meta, u64 before,
                       u64* gen, u64* dist) {
-    unsigned long long* d = nullptr;
-    if (hipMalloc(&d, 2 * MA_NACT * 8) != hipSuccess) return MC_E_OOM;
+    if (res_.device(&d_stop_, 2 * MA_NACT * 8) != hipSuccess) return MC_E_OOM;   // (scratch of this call)
+    unsigned long long* const d = d_stop_;
     int rc = 0;
     if (hipMemsetAsync(d, 0, 2 * MA_NACT * 8, stream_) != hipSuccess) rc = MC_E_NO_DEVICE;
     if (!rc && npar)
@@ -1441,7 +1598,7 @@ class MembGpu : public Backend {
     u64 h[2 * MA_NACT];
     if (!rc && (hipGetLastError() != hipSuccess || hipMemcpyAsync(h, d, sizeof h, hipMemcpyDeviceToHost, stream_) != hipSuccess ||
                 hipStreamSynchronize(stream_) != hipSuccess)) rc = MC_E_NO_DEVICE;
-    (void)hipFree(d);
+    res_.free(&d_stop_);
     if (rc) return rc;
     for (int k = 0; k < MA_NACT; ++k) { gen[k] = h[k]; dist[k] = h[MA_NACT + k]; }
     return 0;
@@ -1475,11 +1632,7 @@ class MembGpu : public Backend {
   int shard_open(const RunOpts& o, int rank, int world, std::string& err) override {
     if (world < 1 || world > 8 || rank < 0 || rank >= world) { err = "world must be 1..8"; return MC_E_INVALID; }
     store_.reset();   // sharded runs keep every state on the device
-    for (int q = 0; q < 2; ++q)
-      if (((m_.rt.constraints >> kPrefixCon[q]) & 1u) && !have_prefix_[q]) {
-        err = std::string(kMembConNames[kPrefixCon[q]]) + " needs its golden history trace (mc_set_history_prefix)";
-        return MC_E_UNSUPPORTED;
-      }
+    if (int rc = require_prefixes(err, " (mc_set_history_prefix)")) return rc;
     RunOpts so = o;
     if (!so.state_store_bytes) {   // leave room for the level records and the sort (see below)
       size_t freeb = 0, totalb = 0;
@@ -1488,61 +1641,34 @@ class MembGpu : public Backend {
     }
     if (int rc = ensure_alloc(so, err)) return rc;
     if (int rc = prepare_prefixes(err)) return rc;
-    rt_host_.sym_tlc = rt_dev_.sym_tlc = (o.sym_tlc && m_.rt.symmetry) ? 1u : 0u;
-    fp_slice_test_ = o.test_fp_slice;
-    rt_host_.disjunct_copies = rt_dev_.disjunct_copies = o.disjunct_copies ? 1u : 0u;
+    apply_run_switches(o);
     sopts_ = o; s_rank_ = rank; s_world_ = world; s_finished_ = false; have_viol_ = false; sres_err_ = 0; sharded_ = true;
     // level records / sorted winners / newrec: lvl_cap_ entries each, plus the sort's scratch
     const u64 sb = so.state_store_bytes;
     const u64 want = std::max<u64>(4096, (sb / 4) / 16);
     if (!d_lvl_ || lvl_cap_ != want) {
-      for (void* q : {(void*)d_lvl_, (void*)d_sorted_, (void*)d_newrec_lvl_, (void*)d_sort_tmp_, (void*)d_nsucc_lvl_}) if (q) (void)hipFree(q);
       lvl_cap_ = want;
-      HIPCHK(hipMalloc(&d_lvl_, lvl_cap_ * 16));
-      HIPCHK(hipMalloc(&d_sorted_, lvl_cap_ * 8));
-      HIPCHK(hipMalloc(&d_newrec_lvl_, lvl_cap_ * 8));
-      HIPCHK(hipMalloc(&d_nsucc_lvl_, store_.cap() * 2));
+      HIPCHK(res_.device(&d_lvl_, lvl_cap_ * 16));
+      HIPCHK(res_.device(&d_sorted_, lvl_cap_ * 8));
+      HIPCHK(res_.device(&d_newrec_lvl_, lvl_cap_ * 8));
+      HIPCHK(res_.device(&d_nsucc_lvl_, store_.cap() * 2));
       sort_tmp_bytes_ = 0;
       HIPCHK(rocprim::radix_sort_keys(nullptr, sort_tmp_bytes_, (const u64*)nullptr, (u64*)nullptr, (size_t)lvl_cap_, 0, 48,
                                       stream_));
-      HIPCHK(hipMalloc(&d_sort_tmp_, std::max<size_t>(sort_tmp_bytes_, 16)));
+      HIPCHK(res_.device(&d_sort_tmp_, std::max<size_t>(sort_tmp_bytes_, 16)));
     }
-    HIPCHK(hipMemsetAsync(d_table_, 0, (table_mask_ + 1) * 16, stream_));
-    HIPCHK(hipStreamSynchronize(stream_));
-    sres_ = RunResult();
-    sres_.seed = o.seed ? o.seed : 0x5EED5EED2024ull;
-    sres_.state_bytes = NWP * 4;
-    for (int k = 0; k < MA_NACT; ++k) sres_.action_names.push_back(kMembActNames[k]);
-    sres_.act_generated.assign(MA_NACT, 0); sres_.act_distinct.assign(MA_NACT, 0);
-    sres_.kernels = {{"memb_expand", 0, 0, 0}, {"memb_fingerprint", 0, 0, 0}, {"memb_dedup_sh", 0, 0, 0},
-                     {"memb_select_sh", 0, 0, 0}, {"memb_materialize", 0, 0, 0}};
+    if (int rc = clear_table(err)) return rc;
+    sres_ = new_result(o.seed, {"memb_expand", "memb_fingerprint", "memb_dedup_sh", "memb_select_sh", "memb_materialize"});
+    pending_.clear();
     t0_ = std::chrono::steady_clock::now();
-    // Init (raft.tla:388-393): every rank evaluates it; rank 0 stores it, its owner seeds the seen-set
-    W s0; S::init(s0);
-    sres_.generated = 1; sres_.depth = 1;
-    sres_.levels.push_back({1, 0, 0.0});
-    s_level_ = 0; s_level_begin_ = 0; s_level_count_ = 0; store_.set_total(0);
-    if (!S::in_model(s0, s0, rt_host_)) { sres_.distinct = 0; sres_.depth = 0; s_finished_ = true; finish(sres_, t0_); return 0; }
-    const u64 fp0 = S::fingerprint(s0, sres_.seed, rt_host_);
-    if (fp_owner(fp0, (u32)world) == (u32)rank) {
-      const u64 e2[2] = {fp0, ~0ull};
-      HIPCHK(hipMemcpy(d_table_ + 2 * (fp0 & table_mask_), e2, 16, hipMemcpyHostToDevice));
-    }
-    if (rank == 0) {
-      u32 w0[S::NW]; S::pack(s0, w0);
-      u32 wp[NWP] = {0}; for (int q = 0; q < S::NW; ++q) wp[q] = w0[q];
-      HIPCHK(hipMemcpy(store_.states(), wp, NWP * 4, hipMemcpyHostToDevice));
-      const u64 nometa = ~0ull;
-      HIPCHK(hipMemcpy(store_.meta(), &nometa, 8, hipMemcpyHostToDevice));
-      store_.set_total(1); s_level_count_ = 1;
-    }
-    sres_.distinct = 1;
-    if (u32 bad = S::check_invariants(s0, rt_host_)) {
-      if ((bad >> 8) == IV_BAD) { sres_.verdict = MC_VERDICT_INVARIANT_VIOLATION; sres_.violated = kMembInvNames[bad & 255]; }
-      else { sres_.verdict = MC_VERDICT_EVAL_ERROR; sres_.error = std::string("TLC evaluation error in invariant ") + kMembInvNames[bad & 255]; }
-      if (rank == 0) { have_viol_ = true; viol_parent_ = ~0ull; viol_act_ = "<Initial predicate>"; viol_text_ = text_.text(s0, true); }
-      s_finished_ = true; s_level_count_ = 0; finish(sres_, t0_);
-    }
+    // Init: every rank evaluates it; rank 0 stores it, its owner seeds the seen-set
+    s_level_ = 0; s_level_begin_ = 0; s_level_count_ = 0;
+    bool ended = false;
+    std::string init_text;
+    if (int rc = seed_init(sres_, rank, world, nullptr, ended, init_text, err)) return rc;
+    s_level_count_ = ended ? 0 : store_.total();
+    if (!init_text.empty() && rank == 0) { have_viol_ = true; viol_parent_ = ~0ull; viol_act_ = "<Initial predicate>"; viol_text_ = init_text; }
+    if (ended) { s_finished_ = true; finish(sres_, t0_); }
     return 0;
   }
   int shard_record_bytes(int what) const override {
@@ -1575,20 +1701,11 @@ class MembGpu : public Backend {
     if (!gen_cnt_) return 0;
     const u64 cnt = gen_cnt_, nslots = cnt * (u64)S::NSLOT;
     const u32 nblk = (u32)((cnt + BS - 1) / BS);
-    MGenArgs g;
-    g.states = store_.states(); g.chunk_begin = s_level_begin_ + gen_begin_; g.chunk_count = cnt; g.rank0 = s_B_ + gen_begin_;
-    g.cand = d_cand_; g.cells = d_cells_; g.cells_oom = d_cells_oom_; g.cell_count = d_cell_count_; g.nsucc = d_nsucc_;
-    g.seed = sres_.seed; g.rt = rt_dev_; g.inv_oom = sopts_.inv_out_of_model ? 1u : 0u;
-    g.deadlock = sopts_.check_deadlock ? 1u : 0u; g.ctr = (unsigned long long*)d_ctr_;
-    g.smask = nullptr;   // the dense cand form: memb_route / memb_dedup_sh / memb_select_sh read every slot
-    HIPCHK(hipEventRecord(ev_[0], stream_));
-    hipLaunchKernelGGL((memb_expand<S>), dim3(nblk), dim3(BS), 0, stream_, g);
-    HIPCHK(hipGetLastError());
-    if (sopts_.inv_out_of_model) hipLaunchKernelGGL((memb_oom_check<S>), dim3(nblk), dim3(BS), 0, stream_, g);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ev_[1], stream_));
+    const MGenArgs g = gen_args(store_.states(), s_level_begin_ + gen_begin_, cnt, s_B_ + gen_begin_, sres_.seed, rt_dev_, sopts_, nullptr);
+    if (int rc = launch_expand(g, nblk, sopts_.inv_out_of_model, sres_, err)) return rc;
+    if (int rc = timed_begin(sres_, 1, 1, err)) return rc;
     if (int rc = launch_fingerprint(g, nblk, err)) return rc;
-    HIPCHK(hipEventRecord(ev_[2], stream_));
+    if (int rc = timed_end(err)) return rc;
     HIPCHK(hipMemcpyAsync(d_nsucc_lvl_ + gen_begin_, d_nsucc_, cnt * 2, hipMemcpyDeviceToDevice, stream_));
     route_.cand = d_cand_; route_.nslots = nslots; route_.chunk_count = cnt; route_.rank0 = s_B_ + gen_begin_;
     route_.nslot = S::NSLOT; route_.world = (u32)s_world_; route_.counts = (unsigned long long*)(d_ctr_ + C_SHARD);
@@ -1599,9 +1716,7 @@ class MembGpu : public Backend {
     u64 c[8];
     HIPCHK(hipMemcpyAsync(c, d_ctr_ + C_SHARD, sizeof c, hipMemcpyDeviceToHost, stream_));
     HIPCHK(hipStreamSynchronize(stream_));
-    sres_.kernels[0].ms += ms(0, 1); sres_.kernels[0].launches++;
-    sres_.kernels[1].ms += ms(1, 2); sres_.kernels[1].launches++;
-    level_ms_ += ms(0, 2);
+    level_ms_ += harvest(sres_);
     for (int q = 0; q < s_world_; ++q) counts[q] = (int64_t)c[q];
     return 0;
   }
@@ -1647,13 +1762,11 @@ class MembGpu : public Backend {
     MDedupShArgs d;
     d.recv = (const u64*)recv; d.n = n; d.level = s_level_ + 1; d.table = d_table_; d.table_mask = table_mask_;
     d.lvl = d_lvl_ + 2 * lvl_n_; d.ctr = (unsigned long long*)d_ctr_;
-    HIPCHK(hipEventRecord(ev_[3], stream_));
+    if (int rc = timed_begin(sres_, 2, 1, err)) return rc;
     hipLaunchKernelGGL(memb_dedup_sh, dim3((unsigned)((n + BS * DPER - 1) / (BS * DPER))), dim3(BS), 0, stream_, d);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ev_[4], stream_));
-    HIPCHK(hipEventSynchronize(ev_[4]));
-    sres_.kernels[2].ms += ms(3, 4); sres_.kernels[2].launches++; sres_.kernels[2].algo_bytes += (double)n * 48;
-    level_ms_ += ms(3, 4);
+    if (int rc = timed_end(err, true)) return rc;
+    level_ms_ += harvest(sres_);
+    sres_.kernels[2].algo_bytes += (double)n * 48;
     lvl_n_ += n;
     return 0;
   }
@@ -1665,15 +1778,14 @@ class MembGpu : public Backend {
     for (int q = 0; q < 8; ++q) sel_.kstart[q] = ks_[q];
     sel_.world = (u32)s_world_; sel_.counts = (unsigned long long*)(d_ctr_ + C_SHARD); sel_.out = nullptr;
     HIPCHK(hipMemsetAsync(d_ctr_ + C_SHARD, 0, 8 * 8, stream_));
-    HIPCHK(hipEventRecord(ev_[3], stream_));
-    hipLaunchKernelGGL((memb_select_sh<false>), dim3((unsigned)((lvl_n_ + BS * RPER - 1) / (BS * RPER))), dim3(BS), 0, stream_, sel_);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ev_[4], stream_));
+    if (int rc = timed(sres_, 3, [&] {
+          hipLaunchKernelGGL((memb_select_sh<false>), dim3((unsigned)((lvl_n_ + BS * RPER - 1) / (BS * RPER))), dim3(BS), 0, stream_, sel_);
+        }, err)) return rc;
     u64 c[8];
     HIPCHK(hipMemcpyAsync(c, d_ctr_ + C_SHARD, sizeof c, hipMemcpyDeviceToHost, stream_));
     HIPCHK(hipStreamSynchronize(stream_));
-    sres_.kernels[3].ms += ms(3, 4); sres_.kernels[3].launches++; sres_.kernels[3].algo_bytes += (double)lvl_n_ * 24;
-    level_ms_ += ms(3, 4);
+    level_ms_ += harvest(sres_);
+    sres_.kernels[3].algo_bytes += (double)lvl_n_ * 24;
     for (int q = 0; q < s_world_; ++q) reply_counts[q] = (int64_t)c[q];
     return 0;
   }
@@ -1686,22 +1798,17 @@ class MembGpu : public Backend {
     if (n > lvl_cap_) { sres_err_ |= MERR_STORE; n_sorted_ = 0; return 0; }
     if (store_.total() + n > store_.cap()) { sres_err_ |= MERR_STORE; n_sorted_ = 0; return 0; }
     size_t tb = sort_tmp_bytes_;
-    HIPCHK(hipEventRecord(ev_[5], stream_));
+    if (int rc = timed_begin(sres_, 4, 1, err)) return rc;   // (the pair holds the sort as well)
     HIPCHK(rocprim::radix_sort_keys(d_sort_tmp_, tb, (const u64*)acks, d_sorted_, (size_t)n, 0, 48, stream_));
     hipLaunchKernelGGL(memb_keys_to_newrec, dim3((unsigned)((n + BS - 1) / BS)), dim3(BS), 0, stream_, (const u64*)d_sorted_, n,
                        (u64)S::NSLOT, s_B_, s_level_begin_, d_newrec_lvl_);
     HIPCHK(hipGetLastError());
-    MMatArgs m;
-    m.states = store_.states(); m.meta = store_.meta(); m.newrec = d_newrec_lvl_; m.n_new = n; m.dst_base = store_.total(); m.cap = store_.cap();
-    m.level_begin = s_level_begin_ - s_B_;   // gid - level_begin = global rank (mod 2^64)
-    m.gid_tag = (u64)s_rank_ << 37; m.rt = rt_dev_; m.ctr = (unsigned long long*)d_ctr_;
-    if (rt_dev_.sym_tlc) hipLaunchKernelGGL((memb_materialize<S, true>), dim3((unsigned)((n + BS - 1) / BS)), dim3(BS), 0, stream_, m);
-    else hipLaunchKernelGGL((memb_materialize<S, false>), dim3((unsigned)((n + BS - 1) / BS)), dim3(BS), 0, stream_, m);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ev_[6], stream_));
-    HIPCHK(hipEventSynchronize(ev_[6]));
-    sres_.kernels[4].ms += ms(5, 6); sres_.kernels[4].launches++; sres_.kernels[4].algo_bytes += (double)n * (8 + 2 * NWP * 4 + 8);
-    level_ms_ += ms(5, 6);
+    // level_begin: gid - level_begin = global rank (mod 2^64)
+    launch_materialize(mat_args(store_.states(), store_.meta(), d_newrec_lvl_, n, store_.total(), store_.cap(), s_level_begin_ - s_B_,
+                                (u64)s_rank_ << 37, rt_dev_));
+    if (int rc = timed_end(err, true)) return rc;
+    level_ms_ += harvest(sres_);
+    sres_.kernels[4].algo_bytes += (double)n * (8 + 2 * NWP * 4 + 8);
     nnew_ = n;
     return 0;
   }
@@ -1874,13 +1981,12 @@ class MembGpu : public Backend {
   u32* d_cells_ = nullptr; u32* d_cells_oom_ = nullptr; u32* d_cell_count_ = nullptr; u32* d_big_ = nullptr;
   u64* d_smask_ = nullptr;   // [SMW][chunk] in-model slot masks (single-GPU loop)
   u64* d_wit_ = nullptr;     // continue mode: the chunk's witness words (memb_witness.hip), allocated by its first run
-  hipEvent_t ev_w_[2] = {};  // ... and memb_witness_new's timing events
+  unsigned long long* d_stop_ = nullptr;   // stop_counts_dev's counters, for the length of a call
   int inv_id_at(u32 q) const { return (int)((rt_host_.inv_order[q / 8] >> (8 * (q % 8))) & 255u); }   // cfg position -> MembInv
   static constexpr int SMW = (S::NSLOT + 63) / 64;
   int fp_slice_test_ = -1;   // RunOpts::test_fp_slice of the current run
   u64* d_bsum_ = nullptr;
   hipStream_t stream_ = nullptr;
-  hipEvent_t ev_[9] = {};
   u64 table_mask_ = 0, chunk_ = 0;
   int dev_ = -1; uint64_t req_table_ = 0, req_store_ = 0;
   StateStore store_;   // the stored states and parent pointers: device part + host spill
@@ -1915,7 +2021,7 @@ class MembGpu : public Backend {
   int launch_fingerprint(MGenArgs g, u32 nblk, std::string& err) {
     g.prof = nullptr;
 #ifdef RMC_FP_PROF
-    if (!d_prof_) { HIPCHK(hipMalloc(&d_prof_, 8 * 8)); HIPCHK(hipMemset(d_prof_, 0, 8 * 8)); }
+    if (!d_prof_) { HIPCHK(res_.device(&d_prof_, 8 * 8)); HIPCHK(hipMemset(d_prof_, 0, 8 * 8)); }
     g.prof = d_prof_;
 #endif
     g.big = d_big_;
@@ -1938,29 +2044,26 @@ class MembGpu : public Backend {
   }
   unsigned long long* d_prof_ = nullptr;   // RMC_FP_PROF builds (printed to stderr by release)
 
+  // owns every device allocation, event and stream named above (and the pool of timing events):
+  // each is created through it, and release() frees them all
+  DevOwner<HipDevApi> res_;
+  std::vector<int> pending_;   // the kernel of each event pair not yet read back (timed_begin / harvest)
+
   void release_device() override { release(); }
   void release() {
+    if (stream_) (void)hipStreamSynchronize(stream_);
     if (d_prof_) {
       unsigned long long h[8] = {0};
       if (hipMemcpy(h, d_prof_, sizeof h, hipMemcpyDeviceToHost) == hipSuccess)
         std::fprintf(stderr, "FP_PROF apply %llu prologue %llu first %llu narrow %llu bagloops %llu tail %llu view %llu\n",
                      h[0], h[1], h[2], h[3], h[4], h[5], h[6]);
-      (void)hipFree(d_prof_);
-      d_prof_ = nullptr;
     }
-    for (auto& p : d_ptab_) { if (p) (void)hipFree(p); p = nullptr; }
-    for (void* q : {(void*)d_lvl_, (void*)d_sorted_, (void*)d_newrec_lvl_, (void*)d_sort_tmp_, (void*)d_nsucc_lvl_}) if (q) (void)hipFree(q);
-    d_lvl_ = nullptr; d_sorted_ = nullptr; d_newrec_lvl_ = nullptr; d_sort_tmp_ = nullptr; d_nsucc_lvl_ = nullptr; lvl_cap_ = 0;
-    for (void* p : {(void*)d_table_, (void*)d_ctr_, (void*)d_cand_, (void*)d_newrec_,
-                    (void*)d_nsucc_, (void*)d_woff_, (void*)d_bsum_, (void*)d_cells_, (void*)d_cells_oom_, (void*)d_cell_count_, (void*)d_big_, (void*)d_smask_})
-      if (p) (void)hipFree(p);
-    for (auto& e : ev_) { if (e) (void)hipEventDestroy(e); e = nullptr; }
-    for (auto& e : ev_w_) { if (e) (void)hipEventDestroy(e); e = nullptr; }
-    if (d_wit_) { (void)hipFree(d_wit_); d_wit_ = nullptr; }
-    if (stream_) (void)hipStreamDestroy(stream_);
+    res_.release();   // streams last
     store_.release();
-    d_table_ = nullptr; d_ctr_ = nullptr; d_cand_ = nullptr; d_newrec_ = nullptr;
-    d_nsucc_ = nullptr; d_woff_ = nullptr; d_bsum_ = nullptr; d_cells_ = nullptr; d_cells_oom_ = nullptr; d_cell_count_ = nullptr; d_big_ = nullptr; d_smask_ = nullptr; stream_ = nullptr;
+    pending_.clear();
+    lvl_cap_ = 0; sort_tmp_bytes_ = 0;
+    sharded_ = false; s_finished_ = true;   // a sharded search cannot go on without its buffers
+    dev_ = -1;   // nothing allocated: the next ensure_alloc starts over
   }
   // a parent pointer: the action in bits 10..19, the parent's global id from bit 20 up
   void build_trace(u64 parent, const char* last_act, const W& last, RunResult& r, std::string& err) {

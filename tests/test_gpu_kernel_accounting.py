@@ -1,4 +1,4 @@
-"""The per-kernel accounting of every raft_original pipeline, number for number (MI355X).
+"""The per-kernel accounting of every raft_original and tlc_membership pipeline, number for number (MI355X).
 
 Result.kernels (launches, algorithmic bytes, event-pair milliseconds) and n_launches are filled
 by the host code that queues each pipeline stage: mc_run's level loop, the sharded step API that
@@ -19,6 +19,13 @@ routed record is received by some rank, so over all ranks
 which is reproducible: for a case with a route pass the fixture holds that difference
 ("dedup_minus_route") in place of the two byte counts (null), and everything else as reported.
 
+The tlc_membership cases (MEMB_CASES, tests/golden/memb_kernel_accounting.json) pin the same three paths
+of class MembGpu as the build before its stage launchers were shared reported them: the plain search in
+both SYMMETRY modes and without the out-of-model invariant pass, a continue-mode search whose levels are
+cut into chunks and whose completed levels spill, the step API and the native FIFO-ranked loop.  Those
+paths keep the minimum key per fingerprint and have no first-come filter: two recordings of that build
+agreed on every number, so the fixture holds all of them as reported.
+
 RAFTMC_RECORD_KERNEL_ACCOUNTING=<path>: test_kernel_accounting_unchanged adds what this build
 reports, pinned() applied, to the JSON file <path> instead of comparing (record twice, to two
 paths, and keep the file only if both recordings are equal).
@@ -29,7 +36,7 @@ import os
 
 import pytest
 
-from oracle_util import CONFIGS, GOLDEN, ORIG_MC
+from oracle_util import CONFIGS, GOLDEN, MEMB_MC, ORIG_MC
 
 pytestmark = pytest.mark.gpu
 
@@ -37,6 +44,9 @@ SIZES = dict(fp_table_bytes=1 << 26, state_store_bytes=1 << 28)
 PAIR = os.path.join(CONFIGS, "parity_pair.cfg")
 C1 = os.path.join(CONFIGS, "c1.cfg")
 FIXTURE = os.path.join(GOLDEN, "orig_kernel_accounting.json")
+MEMB_FIXTURE = os.path.join(GOLDEN, "memb_kernel_accounting.json")
+MEMB_SIZES = dict(fp_table_bytes=1 << 26, state_store_bytes=1 << 29)
+MEMB_TWO = os.path.join(CONFIGS, "memb_two.cfg")
 RECORD = os.environ.get("RAFTMC_RECORD_KERNEL_ACCOUNTING")
 
 
@@ -65,11 +75,43 @@ CASES = {
 }
 
 
-def accounting(results):
+def _memb_single(raftmc, **kw):
+    # the model of test_membership_handle_rerun
+    with raftmc.ModelChecker(MEMB_MC, MEMB_TWO, max_depth=14, deadlock=False, **dict(MEMB_SIZES, **kw)) as mc:
+        return [mc.run()]
+
+
+def _memb_continue_chunked(raftmc, mp):
+    # test_later_chunks_and_spilled_parents' run: the store (and with it the chunk) too small for the search
+    from test_gpu_continue import continue_run
+    from test_gpu_membership import FIX, _spill_store
+    store = _spill_store(raftmc, FIX["tlc:scen_ConcurrentLeaders"], margin=3.1)
+    return [continue_run(raftmc, "scen_all_shipped", "tlc", state_store_bytes=store)]
+
+
+MEMB_KW = dict(max_depth=14, deadlock=False, sym_tlc=True, **MEMB_SIZES)
+MEMB_CASES = {
+    "memb_single_memb_two_orbit": lambda raftmc, mp: _memb_single(raftmc, sym_tlc=False),
+    "memb_single_memb_two_tlc": lambda raftmc, mp: _memb_single(raftmc, sym_tlc=True),
+    "memb_single_memb_two_no_oom_pass": lambda raftmc, mp: _memb_single(raftmc, sym_tlc=True, inv_out_of_model=False),
+    "memb_single_continue_chunked": _memb_continue_chunked,
+    "memb_step_api_world1_memb_two": lambda raftmc, mp: [_shard().check_sharded(MEMB_MC, MEMB_TWO, 0, 1, **MEMB_KW)],
+    "memb_native_loopback_world1_memb_two": lambda raftmc, mp: _shard().check_loopback(MEMB_MC, MEMB_TWO, 1, **MEMB_KW),
+    "memb_native_loopback_world2_memb_two": lambda raftmc, mp: _shard().check_loopback(MEMB_MC, MEMB_TWO, 2, **MEMB_KW),
+}
+# how each family's searches end: raft_original's run out of states, memb_two stops at max_depth and the
+# continue run at the last witness
+VERDICTS = dict({name: "OK" for name in CASES}, **{name: "DEPTH_LIMIT" for name in MEMB_CASES})
+VERDICTS["memb_single_continue_chunked"] = "INVARIANT_VIOLATION"
+FIXTURE_OF = dict({name: FIXTURE for name in CASES}, **{name: MEMB_FIXTURE for name in MEMB_CASES})
+CASES.update(MEMB_CASES)
+
+
+def accounting(results, verdict="OK"):
     """one entry per rank: what the fixture pins"""
     out = []
     for r in results:
-        assert r.verdict == "OK", r.error
+        assert r.verdict == verdict, r.error
         for name, k in r.kernels.items():
             assert k["ms"] > 0 or k["launches"] == 0, (name, k)
         out.append({"n_launches": r.n_launches,
@@ -89,12 +131,13 @@ def pinned(ranks):
 
 
 def test_fixture_covers_every_case():
-    assert sorted(json.load(open(FIXTURE))) == sorted(CASES)
+    for path in (FIXTURE, MEMB_FIXTURE):
+        assert sorted(json.load(open(path))) == sorted(name for name in CASES if FIXTURE_OF[name] == path)
 
 
 @pytest.mark.parametrize("name", sorted(CASES))
 def test_kernel_accounting_unchanged(raftmc, monkeypatch, name):
-    got = accounting(CASES[name](raftmc, monkeypatch))
+    got = accounting(CASES[name](raftmc, monkeypatch), VERDICTS[name])
     print(name, json.dumps(got))
     got = pinned(got)
     if RECORD:
@@ -104,6 +147,10 @@ def test_kernel_accounting_unchanged(raftmc, monkeypatch, name):
             json.dump(rec, f, indent=1, sort_keys=True)
             f.write("\n")
         return
-    assert got == json.load(open(FIXTURE))[name]
+    assert got == json.load(open(FIXTURE_OF[name]))[name]
     if name == "single_c1_overlap256":   # some level was pipelined: more generate launches than levels
         assert got["ranks"][0]["kernels"]["orig_generate"]["launches"] > got["ranks"][0]["n_launches"]
+    if name == "memb_single_continue_chunked":   # levels took several chunks, and the witness kernels ran
+        k = got["ranks"][0]["kernels"]
+        assert k["memb_expand"]["launches"] > got["ranks"][0]["n_launches"]
+        assert k["memb_witness"]["launches"] > 0

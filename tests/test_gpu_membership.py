@@ -146,6 +146,23 @@ def test_membership_handle_rerun(raftmc):
     assert (a.generated, a.distinct, a.actions) == (b.generated, b.distinct, b.actions)
 
 
+def test_membership_release_device_memory(raftmc, tmp_path):
+    """test_gpu.py's test_release_device_memory on a tlc_membership handle: after
+    mc_release_device_memory the last summary stays readable, mc_dump_states is refused, and the
+    next run allocates everything again and gives the same result."""
+    with raftmc.ModelChecker(MEMB_MC, os.path.join(CONFIGS, "memb_two.cfg"), max_depth=14, **SMALL) as mc:
+        a = mc.run()
+        mc.release_device_memory()
+        assert mc.summary().distinct == a.distinct
+        with pytest.raises(raftmc.RaftMCError) as e:
+            mc.dump_states(str(tmp_path / "x.txt"))
+        assert e.value.code == -7
+        b = mc.run()
+        mc.dump_states(str(tmp_path / "y.txt"))
+    assert (a.verdict, a.generated, a.distinct, a.depth, a.actions) == (b.verdict, b.generated, b.distinct, b.depth, b.actions)
+    assert sum(1 for _ in open(tmp_path / "y.txt")) == b.distinct
+
+
 # C3's stop point in both SYMMETRY modes (GPU-measured; the deepest oracle pins of this model are
 # memb_four@16 in tests/golden/memb_parity.json and tests/golden/memb_deep.json).  Generated counts
 # include TLC's copies of disjunctive guards (memb_spec.h tlc_copies; round 5: +4,637,015 / +4,628,184)
