@@ -183,7 +183,9 @@ constexpr PermTables make_perm_tables(int n) {
   }
   return t;
 }
-#if defined(__HIPCC__)
+// (device pass only: in the host pass of a HIP translation unit a __device__ variable is an empty shadow,
+// and host code that indexes it at run time -- perm_of, cand_of -- read zeros instead of the tables)
+#if defined(__HIPCC__) && defined(__HIP_DEVICE_COMPILE__)
 __device__ constexpr PermTables kPermTables[5] = {make_perm_tables(0), make_perm_tables(1), make_perm_tables(2), make_perm_tables(3), make_perm_tables(4)};
 #else
 constexpr PermTables kPermTables[5] = {make_perm_tables(0), make_perm_tables(1), make_perm_tables(2), make_perm_tables(3), make_perm_tables(4)};

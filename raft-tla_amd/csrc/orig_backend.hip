@@ -676,8 +676,14 @@ __global__ void __launch_bounds__(BS) orig_merge(DedupArgs a) {
   }
   const u32 nov = ovf_cnt;   // (read after the scan's barriers)
   __syncthreads();
-  // move the overflow records (end of the region) behind the set's
-  for (u32 q = threadIdx.x; q < nov; q += BS) out[total + q] = out[a.region - 1 - q];
+  // move the overflow records (end of the region) behind the set's.  Their order is free, so when the
+  // two runs meet (total + 2 * nov > region: a region filled by records of few LDS windows) only the
+  // records beyond total + nov move, into the gap below the run: sources and destinations never
+  // overlap, whichever thread runs first.  (Moving all nov of them let one thread overwrite a record
+  // that another had yet to read, which lost fingerprints.)
+  const u32 gap = (u32)a.region - total - nov;
+  const u32 mv = nov < gap ? nov : gap;
+  for (u32 q = threadIdx.x; q < mv; q += BS) out[total + q] = out[a.region - 1 - q];
   if (threadIdx.x == 0) a.ucnt[blockIdx.x] = total + nov;
 }
 
