@@ -115,19 +115,22 @@ struct Backend {
     (void)trace; err = "'" + con + "' is not a constraint of this spec"; return -1;
   }
   // ---- sharded BFS (include/raftmc.h mc_shard_*); rank-local device work only
+  // The step entry points refuse by default (-4, MC_E_UNSUPPORTED): a backend that runs on one GPU
+  // only overrides shard_open (its own message) and shard_result.
   virtual int shard_open(const RunOpts& o, int rank, int world, std::string& err) = 0;
-  virtual int shard_record_bytes(int what) const = 0;
-  virtual int shard_frontier(int64_t* states, int64_t* chunk) const = 0;
-  virtual int shard_generate(int64_t begin, int64_t count, int64_t* counts, std::string& err) = 0;
-  virtual int shard_fill(int what, void* dst, const int64_t* offsets, std::string& err) = 0;
-  virtual int shard_dedup(const void* recv, const int64_t* counts, int64_t* reply_counts, std::string& err) = 0;
-  virtual int shard_materialize(const void* acks, const int64_t* counts, std::string& err) = 0;
-  virtual int shard_store(const void* states, int64_t n, std::string& err) = 0;
-  virtual int shard_level_stats(int64_t* stats, std::string& err) = 0;
-  virtual int shard_level_commit(const int64_t* global, int* done, std::string& err) = 0;
-  virtual int shard_read_state(uint64_t gid, std::string& text, uint64_t* meta, std::string& err) const = 0;
-  virtual int shard_violation(uint64_t* parent, std::string& action, std::string& text) const = 0;
+  virtual int shard_record_bytes(int what) const { (void)what; return 0; }
+  virtual int shard_frontier(int64_t* states, int64_t* chunk) const { (void)states; (void)chunk; return -4; }
+  virtual int shard_generate(int64_t begin, int64_t count, int64_t* counts, std::string& err) { (void)begin; (void)count; (void)counts; return refuse(err); }
+  virtual int shard_fill(int what, void* dst, const int64_t* offsets, std::string& err) { (void)what; (void)dst; (void)offsets; return refuse(err); }
+  virtual int shard_dedup(const void* recv, const int64_t* counts, int64_t* reply_counts, std::string& err) { (void)recv; (void)counts; (void)reply_counts; return refuse(err); }
+  virtual int shard_materialize(const void* acks, const int64_t* counts, std::string& err) { (void)acks; (void)counts; return refuse(err); }
+  virtual int shard_store(const void* states, int64_t n, std::string& err) { (void)states; (void)n; return refuse(err); }
+  virtual int shard_level_stats(int64_t* stats, std::string& err) { (void)stats; return refuse(err); }
+  virtual int shard_level_commit(const int64_t* global, int* done, std::string& err) { (void)global; (void)done; return refuse(err); }
+  virtual int shard_read_state(uint64_t gid, std::string& text, uint64_t* meta, std::string& err) const { (void)gid; (void)text; (void)meta; return refuse(err); }
+  virtual int shard_violation(uint64_t* parent, std::string& action, std::string& text) const { (void)parent; (void)action; (void)text; return -4; }
   virtual const RunResult* shard_result() const = 0;
+  static int refuse(std::string& err) { err = "unsupported"; return -4; }
   // FIFO first-found specs (VIEW): level layout, per-level winner selection, stop-point counters
   // the whole sharded level loop natively over an RCCL communicator (after shard_open)
   virtual int shard_run_native(ShardTransport& t, std::string& err) { (void)t; err = "no native sharded loop for this spec"; return -4; }

@@ -7,20 +7,13 @@
 
 namespace rmc {
 
-// keys_in[0, n) -> keys_out ascending over the low `bits` bits; *tmp / *tmp_bytes grow as needed
+// keys_in[0, n) -> keys_out ascending over the low `bits` bits, with the caller's temporary buffer of
+// *tmp_bytes; tmp == nullptr: nothing is sorted, *tmp_bytes = the temporary bytes this sort needs
 int tlagen_sort_keys(const unsigned long long* keys_in, unsigned long long* keys_out, unsigned long long n, int bits,
-                     void** tmp, size_t* tmp_bytes, hipStream_t s) {
-  size_t need = 0;
-  if (rocprim::radix_sort_keys(nullptr, need, keys_in, keys_out, (size_t)n, 0, bits, s) != hipSuccess) return -1;
-  if (need > *tmp_bytes) {
-    if (*tmp) (void)hipFree(*tmp);
-    *tmp = nullptr;
-    *tmp_bytes = 0;
-    if (hipMalloc(tmp, need) != hipSuccess) return -2;
-    *tmp_bytes = need;
-  }
+                     void* tmp, size_t* tmp_bytes, hipStream_t s) {
   size_t have = *tmp_bytes;
-  if (rocprim::radix_sort_keys(*tmp, have, keys_in, keys_out, (size_t)n, 0, bits, s) != hipSuccess) return -1;
+  if (rocprim::radix_sort_keys(tmp, have, keys_in, keys_out, (size_t)n, 0, bits, s) != hipSuccess) return -1;
+  if (!tmp) *tmp_bytes = have;
   return 0;
 }
 

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include TLG_FILE
+#include "../../raft-tla_amd/csrc/tlagen/tlv_print.h"
 
 using tlv::u32;
 
@@ -52,49 +53,12 @@ struct Emit {
   }
 };
 
-// one-line text of a value / state (raft-tla_amd/csrc/tlagen/tlagen_backend.cpp Printer)
-static std::string vtext(const u32* w) {
-  const u32 tag = w[0] & 7u, n = w[1];
-  switch (tag) {
-    case 1: return w[1] ? "TRUE" : "FALSE";
-    case 2: return std::to_string((long long)(int)(w[1] ^ 0x80000000u));
-    case 3: return tlg::kAtomNames[w[1]];
-    case 4: case 6: {   // set elements sorted by their text (the oracle's print rule, oracle/tla.h show)
-      std::vector<std::string> el;
-      const u32* e = w + 2;
-      for (u32 i = 0; i < n; ++i) { el.push_back(vtext(e)); e += e[0] >> 3; }
-      if (tag == 6) std::sort(el.begin(), el.end());
-      std::string o = tag == 4 ? "<<" : "{";
-      for (u32 i = 0; i < n; ++i) o += (i ? ", " : "") + el[i];
-      return o + (tag == 4 ? ">>" : "}");
-    }
-    default: {
-      bool rec = true;
-      const u32* e = w + 2;
-      for (u32 i = 0; i < n; ++i) {
-        if ((e[0] & 7u) != 3 || tlg::kAtomNames[e[1]][0] != '"') rec = false;
-        e += e[0] >> 3; e += e[0] >> 3;
-      }
-      std::vector<std::pair<std::string, std::string>> fs;   // fields / pairs sorted by text
-      e = w + 2;
-      for (u32 i = 0; i < n; ++i) {
-        const u32* val = e + (e[0] >> 3);
-        if (rec) { std::string k = tlg::kAtomNames[e[1]]; fs.push_back({k.substr(1, k.size() - 2), vtext(val)}); }
-        else fs.push_back({vtext(e), vtext(val)});
-        e = val + (val[0] >> 3);
-      }
-      std::sort(fs.begin(), fs.end());
-      std::string o = rec ? "[" : "(";
-      for (u32 i = 0; i < n; ++i) o += (i ? (rec ? ", " : " @@ ") : "") + fs[i].first + (rec ? " |-> " : " :> ") + fs[i].second;
-      return o + (rec ? "]" : ")");
-    }
-  }
-}
+// one-line text of a state: the library's printer (tlv_print.h) over the generated name tables
+// (each closed by a nullptr)
 static std::string state_text(const std::vector<u32>& w) {
-  std::string o;
-  const u32* p = w.data();
-  for (int i = 0; i < tlg::NV; ++i) { o += (i ? " " : "") + std::string("/\\ ") + tlg::kVarNames[i] + " = " + vtext(p); p += p[0] >> 3; }
-  return o;
+  constexpr size_t natoms = sizeof(tlg::kAtomNames) / sizeof(tlg::kAtomNames[0]) - 1;
+  return tlvprint::printer([](u32 i) { return i < natoms ? tlg::kAtomNames[i] : nullptr; },
+                           [](size_t i) { return tlg::kVarNames[i]; }, (size_t)tlg::NV).state(w.data(), " ");
 }
 
 static void load(tlg::Cx& c, const std::vector<u32>& w) {
