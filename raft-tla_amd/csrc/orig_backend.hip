@@ -83,6 +83,16 @@ enum { OE_CAP_STORE = 0x100, OE_TABLE_FULL = 0x200 };
 constexpr int DEDUP_PER = 4;                  // probes in flight per dedup thread
 constexpr int BS = 256;                       // workgroup size of every kernel (4 waves)
 constexpr int LDS_FP_SLOTS = 2048;            // workgroup-local fingerprint set (8 B fp + 4 B key per slot)
+// orig_dedup_plain beside a generate (profiles/r09_overlap_third_wave_ab.txt): 2 probes in
+// flight per thread bring a wave from 56 to 32 VGPRs, so that 4 dedup waves and 3 generate waves (128 each)
+// fill a SIMD's 512 where two generate waves fitted before, and the 4096-slot filter's 32 KB are what holds
+// a CU to 4 dedup workgroups (of 160 KB): C2 22.3 -> 21.0 ms per run.  The filter is the launch's dynamic
+// LDS: as a static array it tells the compiler that 4 waves per SIMD is the most, and the compiler then
+// raises the wave's register allocation to the most that allows 4 (104, with 30 in use), which leaves no
+// room for any generate wave (22.8 ms).
+constexpr int OVERLAP_DEDUP_PER = 2;
+constexpr int OVERLAP_LDS_FP_SLOTS = 4096;
+constexpr unsigned OVERLAP_FILTER_LDS = OVERLAP_LDS_FP_SLOTS * 8;   // dynamic LDS of the launch beside a generate
 constexpr int MAT_CAP = 2048;      // winners staged in LDS per materialize round
 #ifndef RMC_RV_PATCH
 #define RMC_RV_PATCH 0
@@ -736,19 +746,24 @@ __global__ void __launch_bounds__(BS) orig_probe(DedupArgs a) {
 // inserting thread numbers its new state directly.
 
 // Fused variant for TLC -workers N (what the pipeline runs): records through a first-come LDS
-// filter (lds_first: an LDS CAS claims each empty slot, 16 KB; a full window lets a record through to the
-// seen-set, never drop a state), the survivors probe the 8-B seen-set DEDUP_PER at a time, and
-// the new states' producers go out parent-major (an LDS winner mask per parent).  COUNT: also count the
+// filter (lds_first: an LDS CAS claims each empty slot, 8 B per slot; a full window lets a record through to
+// the seen-set, never drop a state), the survivors probe the 8-B seen-set PER at a time, and
+// the new states' producers go out parent-major (an LDS winner mask per parent).  PER, SLOTS: DEDUP_PER and
+// LDS_FP_SLOTS on a launch of its own, OVERLAP_DEDUP_PER and OVERLAP_LDS_FP_SLOTS beside a generate
+// (launch_dedup_plain); DYN: the filter is the launch's dynamic LDS (SLOTS * 8 B), not a static array
+// (OVERLAP_DEDUP_PER's comment).  COUNT: also count the
 // fingerprints that reach the seen-set (ctr[K_PROBES], one atomic per workgroup) -- a separate
 // instantiation, because even one extra same-address atomic per wave costs ~3 ms of C2's
 // 11 ms here (round 4, measured), so timed runs leave it off (RAFTMC_COUNT_PROBES).
-template <int WW, bool COUNT>
+template <int WW, bool COUNT, int PER = DEDUP_PER, int SLOTS = LDS_FP_SLOTS, bool DYN = false>
 __global__ void __launch_bounds__(BS) orig_dedup_plain(DedupArgs a) {
-  __shared__ unsigned long long lfp[LDS_FP_SLOTS];
+  __shared__ unsigned long long lfp_static[DYN ? 1 : SLOTS];
+  extern __shared__ unsigned long long lfp_dynamic[];
+  unsigned long long* const lfp = DYN ? lfp_dynamic : lfp_static;
   __shared__ u32 wave_tot[BS / 64];
   __shared__ unsigned long long base_sh;
   __shared__ unsigned long long win[BS * WW];
-  for (int t = threadIdx.x; t < LDS_FP_SLOTS; t += BS) lfp[t] = 0ull;
+  for (int t = threadIdx.x; t < SLOTS; t += BS) lfp[t] = 0ull;
   for (int t = threadIdx.x; t < BS * WW; t += BS) win[t] = 0ull;
   __syncthreads();
   const WaveRegions wr(a.rcnt + 4 * blockIdx.x, a.region / 4);
@@ -758,25 +773,25 @@ __global__ void __launch_bounds__(BS) orig_dedup_plain(DedupArgs a) {
   u32 err = 0;
   u32 probes = 0;   // this lane's (summed over the wave at the end)
 #pragma unroll 1
-  for (u32 i0 = 0; i0 < n; i0 += DEDUP_PER * BS) {
-    u64 fp[DEDUP_PER], key[DEDUP_PER], pos[DEDUP_PER];
+  for (u32 i0 = 0; i0 < n; i0 += PER * BS) {
+    u64 fp[PER], key[PER], pos[PER];
 #pragma unroll
-    for (int j = 0; j < DEDUP_PER; ++j) {
+    for (int j = 0; j < PER; ++j) {
       const u32 i = i0 + (u32)j * BS + threadIdx.x;
       const u64 at = wr.at(i);
       fp[j] = i < n ? fps[at] : 0ull;
       key[j] = i < n ? (u64)keys[at] : 0ull;     // local key lane << 8 | instance
     }
 #pragma unroll
-    for (int j = 0; j < DEDUP_PER; ++j)
-      if (fp[j] && !lds_first(lfp, fp[j])) fp[j] = 0ull;   // produced by this workgroup's parents before
+    for (int j = 0; j < PER; ++j)
+      if (fp[j] && !lds_first<SLOTS>(lfp, fp[j])) fp[j] = 0ull;   // produced by this workgroup's parents before
     if constexpr (COUNT) {
 #pragma unroll
-      for (int j = 0; j < DEDUP_PER; ++j) probes += fp[j] ? 1u : 0u;
+      for (int j = 0; j < PER; ++j) probes += fp[j] ? 1u : 0u;
     }
-    const u32 ins = probe_batch<DEDUP_PER, false, 1>(a.table, a.table_mask, fp, key, pos, err);
+    const u32 ins = probe_batch<PER, false, 1>(a.table, a.table_mask, fp, key, pos, err);
 #pragma unroll
-    for (int j = 0; j < DEDUP_PER; ++j)
+    for (int j = 0; j < PER; ++j)
       if ((ins >> j) & 1u) atomicOr(&win[(key[j] >> 8) * WW + ((key[j] & 255) >> 6)], 1ull << (key[j] & 63));
   }
   __shared__ u32 wave_probes[BS / 64];
@@ -1511,14 +1526,6 @@ class OrigGpu : public Backend {
   // 4 GiB clear has just ended, and its own clear and orig_migrate's walk (64 MiB each) are the
   // cheapest; 2^24 and 2^25 stay one level longer, 2^26 two, and pay 2x to 8x for both.
   static constexpr u64 STARTER_SLOTS = 1ull << 23, STARTER_FACTOR = 8;
-  // Generate beside dedup: unused dynamic LDS on orig_dedup_plain's launch beside a
-  // generate, so that 4 of its workgroups fit a CU (18.5 KB static + 17.5 KB = 36 KB of 160 KB) instead
-  // of 8.  The dispatcher gives freed wave slots to whatever fits first, and a dedup workgroup (4 x 56
-  // VGPRs) fits long before a generate workgroup (4 x 112): uncapped, the probes take the whole
-  // device and generate advances at a fifth of its speed until they end.  At 4 per CU two generate
-  // waves per SIMD fit beside them.  Measured on C2 (profiles/r08_generate_dedup_overlap_ab.txt):
-  // no pad 23.4-23.8 ms, 6 per CU 23.0, 5 22.6-23.0, 4 22.2-22.7, 3 22.7-22.9; parent 23.3.
-  static constexpr unsigned OVERLAP_DEDUP_PAD_LDS = 17920;
   int ensure_starter(u64 slots, std::string& err) {
     if (d_starter_ && starter_cap_ == slots) return 0;
     if (d_starter_) HIPCHK(hipStreamSynchronize(stream_));
@@ -1579,10 +1586,19 @@ class OrigGpu : public Backend {
     d.prof = prof_ ? 1u : 0u;
     return d;
   }
-  // dyn: unused dynamic LDS that caps the workgroups per CU (OVERLAP_DEDUP_PAD_LDS)
-  void launch_dedup_plain(const DedupArgs& d, unsigned nblk, unsigned dyn, bool count_probes) {
-    if (count_probes) hipLaunchKernelGGL((orig_dedup_plain<WW, true>), dim3(nblk), dim3(BS), dyn, stream_, d);
-    else hipLaunchKernelGGL((orig_dedup_plain<WW, false>), dim3(nblk), dim3(BS), dyn, stream_, d);
+  // beside_generate: the instantiation that shares a CU with orig_generate.  The
+  // dispatcher gives freed wave slots to whatever fits first, and a dedup workgroup fits long before a
+  // generate workgroup (4 x 128 VGPRs): 8 per CU take the whole device and generate advances at a fifth of
+  // its speed until the probes end.  The 4096-slot filter holds a CU to 4 (the best of 3 to 6 at either
+  // batch size), and at 2 probes per thread (4 x 32 VGPRs) three generate waves per SIMD fit beside them
+  void launch_dedup_plain(const DedupArgs& d, unsigned nblk, bool beside_generate, bool count_probes) {
+    if (beside_generate) {
+      if (count_probes) hipLaunchKernelGGL((orig_dedup_plain<WW, true, OVERLAP_DEDUP_PER, OVERLAP_LDS_FP_SLOTS, true>), dim3(nblk), dim3(BS), OVERLAP_FILTER_LDS, stream_, d);
+      else hipLaunchKernelGGL((orig_dedup_plain<WW, false, OVERLAP_DEDUP_PER, OVERLAP_LDS_FP_SLOTS, true>), dim3(nblk), dim3(BS), OVERLAP_FILTER_LDS, stream_, d);
+    } else {
+      if (count_probes) hipLaunchKernelGGL((orig_dedup_plain<WW, true>), dim3(nblk), dim3(BS), 0, stream_, d);
+      else hipLaunchKernelGGL((orig_dedup_plain<WW, false>), dim3(nblk), dim3(BS), 0, stream_, d);
+    }
   }
 
   // the -workers N store pass: the new states of a chunk of cnt parents, from the positions
@@ -2111,10 +2127,10 @@ class OrigGpu : public Backend {
       }
       // the seen-set pass, then the store pass: each one sequence per search order.  Beside a generate
       // (every pipelined sub-chunk but the level's last) the -workers N probes run at 4 workgroups per
-      // CU, not 8: see OVERLAP_DEDUP_PAD_LDS
+      // CU, not 8, with 2 probes in flight per thread, not 4: see launch_dedup_plain
       const DedupArgs d = dedup_args(g, cb, s.tbl, s.tmask);
       if (s.fifo) { if (int rc = queue_merge_probe(s, d, nblk, err)) return rc; }
-      else launch_dedup_plain(d, nblk, s.ovl && q + 1 < nchunks ? OVERLAP_DEDUP_PAD_LDS : 0u, s.count_probes);
+      else launch_dedup_plain(d, nblk, s.ovl && q + 1 < nchunks, s.count_probes);
       HIPCHK(hipGetLastError());
       HIPCHK(hipEventRecord(e[3], stream_));
       if (s.fifo) { if (int rc = queue_winners_materialize(s, cb, cnt, nblk, e[5], err)) return rc; }
@@ -2952,7 +2968,7 @@ class OrigGpu : public Backend {
           if (int rc = stage_generate(g, nblk, err)) return rc;
           DedupArgs d = dedup_args(g, sh_chunk_begin_, d_table_, sh_table_mask());
           d.prof = 0;   // (RAFTMC_PROF reads the counters of mc_run's levels only)
-          if (int rc = timed(2, [&] { launch_dedup_plain(d, nblk, 0, false); }, err)) return rc;
+          if (int rc = timed(2, [&] { launch_dedup_plain(d, nblk, false, false); }, err)) return rc;
           const MatPlainArgs m = mat_plain_args(0, sh_next_write_, !last);
           if (int rc = timed(3, [&] { launch_materialize_plain(m, count); }, err)) return rc;
           hipLaunchKernelGGL(orig_advance, dim3(1), dim3(64), 0, stream_, (unsigned long long*)d_ctr_, 1);
