@@ -62,6 +62,8 @@ extern "C" {
 #define MC_VERDICT_CAPACITY_OVERFLOW 3
 #define MC_VERDICT_DEADLOCK 4
 #define MC_VERDICT_DEPTH_LIMIT 5
+/* a step breaks a listed PROPERTY of the form [][A]_vars (raft_original; exit code 12, `violated` names it) */
+#define MC_VERDICT_ACTION_PROPERTY_VIOLATION 6
 
 /* tlc_compat_flags: the [ext] TLC-semantics switches */
 #define MC_COMPAT_INV_OUT_OF_MODEL 0x1u /* check invariants on !seen successors that fail a constraint (TLC default) */

@@ -68,6 +68,7 @@ const char* verdict_name(int v) {
     case MC_VERDICT_CAPACITY_OVERFLOW: return "CAPACITY_OVERFLOW";
     case MC_VERDICT_DEADLOCK: return "DEADLOCK";
     case MC_VERDICT_DEPTH_LIMIT: return "DEPTH_LIMIT";
+    case MC_VERDICT_ACTION_PROPERTY_VIOLATION: return "ACTION_PROPERTY_VIOLATION";
   }
   return "?";
 }
@@ -154,6 +155,8 @@ int mc_open(const char* tla_path, const char* cfg_path, const mc_opts* o, mc_ctx
     if (!cfg.symmetry.empty()) cfg.symmetry_def = rmc::definition_text(tla_path, cfg.symmetry);
     if (fam == "raft_original")
       for (const auto& n : cfg.invariants) cfg.invariant_defs.push_back(rmc::definition_text(tla_path, n));
+    if (fam == "raft_original")
+      for (const auto& n : cfg.properties) cfg.property_defs.push_back(rmc::definition_text(tla_path, n));
     // count_final_level exists for raft_original's -workers N search with a depth bound (single GPU
     // or sharded): anywhere else it would be silently ignored, so it is refused
     if (o->count_final_level && (fam != "raft_original" || o->workers == 1 || o->max_depth <= 0))
@@ -449,6 +452,10 @@ int mc_report(const mc_ctx* c, char** text, size_t* len) {
   } else if (r.verdict == MC_VERDICT_INVARIANT_VIOLATION) {
     o << "Error: Invariant " << r.violated << " is violated.\n";
     o << "Error: The behavior up to this point is:\n" << trace_text(c, r);
+  } else if (r.verdict == MC_VERDICT_ACTION_PROPERTY_VIOLATION) {
+    // the behaviour's last two states are the step that breaks the property
+    o << "Error: Action property " << r.violated << " is violated.\n";
+    o << "Error: The behavior up to this point is:\n" << trace_text(c, r);
   } else if (r.verdict == MC_VERDICT_DEADLOCK) {
     o << "Error: Deadlock reached.\nError: The behavior up to this point is:\n" << trace_text(c, r);
   } else if (r.verdict == MC_VERDICT_EVAL_ERROR) {
@@ -555,7 +562,7 @@ int mc_exit_code(const mc_ctx* c) {
   if (!c || !c->ran) return 75;
   switch (c->res.verdict) {
     case MC_VERDICT_OK: case MC_VERDICT_DEPTH_LIMIT: return 0;
-    case MC_VERDICT_INVARIANT_VIOLATION: return 12;
+    case MC_VERDICT_INVARIANT_VIOLATION: case MC_VERDICT_ACTION_PROPERTY_VIOLATION: return 12;
     case MC_VERDICT_DEADLOCK: return 11;
     default: return 75;
   }

@@ -42,6 +42,9 @@ struct CfgFile {
   // module and the modules it EXTENDS do not define it); filled by mc_open for raft_original, whose
   // safety invariants are accepted only from a module that states them (orig_model.cpp)
   std::vector<std::string> invariant_defs;
+  // per PROPERTY name, the same lookup: raft_original accepts a compiled action property only from a
+  // module that states it (orig_model.cpp)
+  std::vector<std::string> property_defs;
   bool has(const std::string& n) const;
   const CVal& get(const std::string& n) const;
 };

@@ -114,6 +114,21 @@ __device__ __forceinline__ void static_for(F&& f) {
 // 64-bit event word: key << 2 | kind, key = parent gid << 8 | instance (gid < 2^40)
 RMC_HD u64 ev_word(u64 gid, u32 inst, u32 kind) { return (((gid << 8) | (u64)inst) << 2) | (u64)kind; }
 
+// Does the step (s, t) of instance k (action act) break a listed action property ([][A]_vars, orig_spec.h
+// §14)?  Compiled into the kernels over WithActions<..> only (S::ACTIONS): in every other instantiation it
+// is the constant false and leaves no code.  Only the properties the action can break are evaluated
+// (S::act_frame).  A violation raises the event word of an invariant violation at the same key.
+template <class S>
+__device__ __forceinline__ bool action_step_violated(const typename S::Work& s, const typename S::Work& t, int k, int act,
+                                                     const OrigRuntime& rt) {
+  if constexpr (S::ACTIONS) {
+    const u32 m = rt.action_props & S::act_frame(act);
+    return m != 0u && S::violated_action(s, t, k, m) != 0u;
+  } else {
+    return false;
+  }
+}
+
 struct GenArgs {
   const u32* states;           // device store [cap][NWP]
   u64 chunk_begin, chunk_count;   // device index of the chunk's first parent, parents
@@ -147,7 +162,7 @@ struct GenArgs {
 // Larger states (C5: 24 words) get no hint and keep the plain hash (the base terms would cost them
 // occupancy: 45 vs 38 ms of expand time for C5 to depth 12).
 template <class S>
-__global__ void __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(S::NW <= 15 ? 4 : 1))) orig_generate(GenArgs a) {
+__global__ void __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(S::GEN_WAVES))) orig_generate(GenArgs a) {
   using W = typename S::Work;
   constexpr int NW = S::NW, NWP = (S::NW + 3) & ~3;
   __shared__ unsigned int lds_cnt[OA_NACT + 1];   // per-action generated, in-model total
@@ -300,10 +315,12 @@ __global__ void __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(S::NW <
         for (int q = 0; q < S::AW; ++q) t.allLogs[q] = al[q];
         ++nsucc;
         atomicAdd(&lds_cnt[act], 1u);
+        const bool step_bad = action_step_violated<S>(s, t, k, act, a.rt);
         if (S::in_model(t, a.rt)) {
           ++nin;
           have = fingerprint(t, fp);
-        } else if (a.inv_oom && S::violated(t, a.rt.invariants & S::inv_frame(act))) {
+          if (step_bad) { const u64 e = ev_word(gid, (u32)k, EV_VIOLATION); ev = e < ev ? e : ev; }
+        } else if (a.inv_oom && (step_bad || S::violated(t, a.rt.invariants & S::inv_frame(act)))) {
           // TLC checks invariants on out-of-model successors ([ext] switch (ii)); first in key order wins
           // (only those the action can change: the parent satisfies all of them, S::inv_frame)
           const u64 e = ev_word(gid, (u32)k, EV_VIOLATION);
@@ -448,8 +465,10 @@ __global__ void __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(S::LEAD
       for (int q = 0; q < S::AW; ++q) t.allLogs[q] = al[q];
       ++nsucc;
       atomicAdd(&lds_cnt[act], 1u);
+      const bool step_bad = action_step_violated<S>(s, t, k, act, a.rt);
       if (S::in_model(t, a.rt)) {
         ++nin;
+        if (step_bad) { const u64 e = ev_word(gid, (u32)k, EV_VIOLATION); ev = e < ev ? e : ev; }
         u32 pw[NW];
         S::pack(t, pw);
         u64 fp;
@@ -463,7 +482,7 @@ __global__ void __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(S::LEAD
         const u32 idx = atomicAdd(wcnt, 1u);
         a.rfp[wreg + idx] = fp;
         a.rkey[wreg + idx] = (unsigned short)((plane << 8) | (unsigned)k);
-      } else if (a.inv_oom && S::violated(t, a.rt.invariants & S::inv_frame(act))) {
+      } else if (a.inv_oom && (step_bad || S::violated(t, a.rt.invariants & S::inv_frame(act)))) {
         const u64 e = ev_word(gid, (u32)k, EV_VIOLATION);
         ev = e < ev ? e : ev;
       }
@@ -1429,6 +1448,10 @@ class OrigGpu : public Backend {
   // of them (safety()); a run that lists none launches the <S> kernels, whose code holds none of it
   using SS = WithSafety<S>;
   bool safety() const { return (m_.rt.invariants & OI_SAFETY_MASK) != 0; }
+  // ... and with the action properties (orig_spec.h §14) as well: what the host evaluates a step with, and
+  // (over S or SS) the instantiation of the generate and simulate kernels when the cfg lists PROPERTIES
+  using SA = WithActions<SS>;
+  bool actions() const { return m_.rt.action_props != 0; }
   static constexpr int NWP = (S::NW + 3) & ~3;
   explicit OrigGpu(const OrigModel& m) : m_(m) {}
   ~OrigGpu() override { release(); }
@@ -1457,6 +1480,12 @@ class OrigGpu : public Backend {
     // only under SYMMETRY (the description is also the checkpoint's model identity: a symmetric file
     // does not resume an unsymmetric search, nor the reverse, and unsymmetric files stay as they were)
     if (m_.rt.symmetry) o << ", \"symmetry\": true, \"permutations\": " << S::NPERM;
+    // only with PROPERTIES, for the same reason: a checkpoint written with them does not resume without
+    if (!m_.prop_names.empty()) {
+      o << ", \"properties\": [";
+      for (size_t k = 0; k < m_.prop_names.size(); ++k) o << (k ? ", " : "") << "\"" << m_.prop_names[k] << "\"";
+      o << "]";
+    }
     o << "}";
     return o.str();
   }
@@ -1555,10 +1584,13 @@ class OrigGpu : public Backend {
   // device); K_LEAD must be zero before (level start: orig_reset_ctr, later chunks: orig_advance, or
   // on a pipelined level the generate stream's own re-arm)
   void launch_generate(const GenArgs& g, unsigned nblk, hipStream_t st) {
-    if (safety()) launch_generate_as<SS>(g, nblk, st);
+    if (actions()) {
+      if (safety()) launch_generate_as<WithActions<SS>>(g, nblk, st);
+      else launch_generate_as<WithActions<S>>(g, nblk, st);
+    } else if (safety()) launch_generate_as<SS>(g, nblk, st);
     else launch_generate_as<S>(g, nblk, st);
   }
-  template <class K>   // K: S or SS
+  template <class K>   // K: S or SS, or WithActions of either
   void launch_generate_as(const GenArgs& g, unsigned nblk, hipStream_t st) {
     if (m_.rt.symmetry) {   // orbit fingerprints, every instance in one kernel (orig_sym.hip)
       hipLaunchKernelGGL((orig_generate_sym<K>), dim3(nblk), dim3(BS), 0, st, g);
@@ -1766,8 +1798,8 @@ class OrigGpu : public Backend {
   int sim_walk(const RunOpts& o, int64_t walk, std::string& text, std::string& err) override {
     if (int rc = sim_check(o, err)) return rc;
     if (walk < 0 || walk >= SIM_MAX_WALKS) { err = "simulation: walk number out of range"; return MC_E_INVALID; }
-    SimWalk<SS> w;
-    sim_replay<SS>(m_.rt, o.inv_out_of_model, o.check_deadlock, o.seed, (u64)walk, sim_depth(o), w);
+    SimWalk<SA> w;
+    sim_replay<SA>(m_.rt, o.inv_out_of_model, o.check_deadlock, o.seed, (u64)walk, sim_depth(o), w);
     text.clear();
     for (const W& st : w.states) { text += state_text(st, false); text += "\n"; }
     return 0;
@@ -1811,7 +1843,10 @@ class OrigGpu : public Backend {
       a.inv_oom = o.inv_out_of_model ? 1u : 0u; a.deadlock = o.check_deadlock ? 1u : 0u; a.ctr = d.ctr;
       HIPCHK(hipEventRecord(d.e0, nullptr));
       const dim3 grid((unsigned)((n + BS - 1) / BS));
-      if (safety()) hipLaunchKernelGGL((orig_simulate<SS>), grid, dim3(BS), 0, nullptr, a);
+      if (actions()) {
+        if (safety()) hipLaunchKernelGGL((orig_simulate<WithActions<SS>>), grid, dim3(BS), 0, nullptr, a);
+        else hipLaunchKernelGGL((orig_simulate<WithActions<S>>), grid, dim3(BS), 0, nullptr, a);
+      } else if (safety()) hipLaunchKernelGGL((orig_simulate<SS>), grid, dim3(BS), 0, nullptr, a);
       else hipLaunchKernelGGL((orig_simulate<S>), grid, dim3(BS), 0, nullptr, a);
       HIPCHK(hipGetLastError());
       HIPCHK(hipEventRecord(d.e1, nullptr));
@@ -1840,8 +1875,8 @@ class OrigGpu : public Backend {
     if (event != ~0ull) {
       // the winning walk again, on the host, with the same spec code and draws
       const u64 walk = sim_event_walk(event);
-      SimWalk<SS> w;
-      sim_replay<SS>(m_.rt, o.inv_out_of_model, o.check_deadlock, o.seed, walk, depth, w);
+      SimWalk<SA> w;
+      sim_replay<SA>(m_.rt, o.inv_out_of_model, o.check_deadlock, o.seed, walk, depth, w);
       if (w.event != event) {
         err = "simulation: the host replay of walk " + std::to_string(walk) + " does not reproduce the device's event";
         return MC_E_STATE;
@@ -1849,8 +1884,7 @@ class OrigGpu : public Backend {
       r.sim_event_walk = (int64_t)walk;
       const u32 kind = sim_event_kind(event);
       if (kind == EV_VIOLATION) {
-        r.verdict = MC_VERDICT_INVARIANT_VIOLATION;
-        r.violated = first_violated(SS::violated(w.states.back(), m_.rt.invariants));
+        name_violation(w.states[w.states.size() - 2], w.states.back(), (int)sim_event_inst(event), o.inv_out_of_model, r.verdict, r.violated);
       } else if (kind == EV_DEADLOCK) {
         r.verdict = MC_VERDICT_DEADLOCK;
       } else {
@@ -1939,7 +1973,7 @@ class OrigGpu : public Backend {
         // matters when it cut off states that come before the event in key order
         const u64 stored = std::min<u64>(nnew, store_.cap() - std::min<u64>(store_.cap(), level_end - store_.base()));
         bool decided = false;
-        if (int rc = handle_event(c[K_EVENT], s.level_begin, s.level_count, nnew, stored, r, decided, err)) return rc;
+        if (int rc = handle_event(c[K_EVENT], s.level_begin, s.level_count, nnew, stored, o.inv_out_of_model, r, decided, err)) return rc;
         if (decided) { store_.set_total(level_end + stored); break; }
       }
       if (c[K_ERR]) {
@@ -2251,7 +2285,7 @@ class OrigGpu : public Backend {
     if (rc == 0 && r.verdict == MC_VERDICT_CAPACITY_OVERFLOW) {
       // the FIFO re-search stores every level (count_final_level included): when it does not
       // fit, the event the -workers N pass found is still reported, not lost
-      static const char* const kind[4] = {"an evaluation error", "a deadlock", "an invariant evaluation error", "an invariant violation"};
+      static const char* const kind[4] = {"an evaluation error", "a deadlock", "an invariant evaluation error", "an invariant or action property violation"};
       r.error = std::string("the -workers N search found ") + kind[evw & 3] + " at depth " + std::to_string(ev_depth) +
                 "; TLC's single-worker re-search of it (for TLC's counterexample and stop point) ran out of capacity: " + r.error;
     }
@@ -2283,7 +2317,7 @@ class OrigGpu : public Backend {
   // = the level's parents after it + the new states found before it.
   // stored: how many of the level's nnew new states the store holds (a prefix in key order);
   // decided = false when the event may lie behind states the full store cut off
-  int handle_event(u64 ev, u64 level_begin, u64 level_count, u64 nnew, u64 stored, RunResult& r, bool& decided,
+  int handle_event(u64 ev, u64 level_begin, u64 level_count, u64 nnew, u64 stored, bool inv_oom, RunResult& r, bool& decided,
                    std::string& err) {
     const int kind = (int)(ev & 3);
     const u64 key = ev >> 2, pg = key >> 8;
@@ -2354,8 +2388,7 @@ class OrigGpu : public Backend {
     }
     W t;
     const int act = successor(s, (int)k, t);
-    r.verdict = MC_VERDICT_INVARIANT_VIOLATION;
-    r.violated = first_violated(SS::violated(t, m_.rt.invariants));
+    name_violation(s, t, (int)k, inv_oom, r.verdict, r.violated);
     r.depth += 1;
     build_trace(pg, act >= 0 ? kOrigActNames[act] : "?", t, r, err);
     if (progress_) std::fprintf(stderr, "trace of %zu states: %.3f s\n", r.trace.size(), since());
@@ -2758,7 +2791,23 @@ class OrigGpu : public Backend {
     sh_event_ = c[K_EVENT];
     const int kind = sh_event_ == ~0ull ? -1 : (int)(sh_event_ & 3);
     st[3] = (int64_t)(c[K_ERR] | (sh_next_write_ > store_.cap() ? (u64)OE_CAP_STORE : 0ull) | (kind == EV_NEXT_ERROR ? (u64)OE_EVAL_LOG_INDEX : 0ull));
-    st[4] = kind == EV_VIOLATION ? 1 : 0; st[5] = kind == EV_DEADLOCK ? 1 : 0; st[6] = (int64_t)sh_level_count_;
+    // [4] is max-reduced over the ranks: 2 = an invariant, 1 = an action property (orig_spec.h §14) -- TLC
+    // checks invariants before implied actions, so an invariant on any rank names the stop
+    sviol_act_.clear(); sviol_verdict_ = 0;
+    if (kind == EV_VIOLATION) {
+      // this rank's violating step, re-derived from (parent, instance)
+      const u64 key = sh_event_ >> 2, par = key >> 8;
+      const int k = (int)(key & 255);
+      u32 w[NWP];
+      HIPCHK(hipMemcpy(w, store_.states() + par * NWP, NWP * 4, hipMemcpyDeviceToHost));
+      W s, t; S::unpack(w, s);
+      const int act = successor(s, k, t);
+      name_violation(s, t, k, sopts_.inv_out_of_model, sviol_verdict_, sviol_name_);
+      sviol_parent_ = ((u64)rank_ << 37) | par; sviol_act_ = act >= 0 ? kOrigActNames[act] : "?";
+      sviol_text_ = state_text(t, true);
+    }
+    st[4] = kind != EV_VIOLATION ? 0 : sviol_verdict_ == MC_VERDICT_ACTION_PROPERTY_VIOLATION ? 1 : 2;
+    st[5] = kind == EV_DEADLOCK ? 1 : 0; st[6] = (int64_t)sh_level_count_;
     return 0;
   }
 
@@ -2782,7 +2831,10 @@ class OrigGpu : public Backend {
       sres_.distinct += g[0];
       if (g[0] > 0) { sres_.levels.push_back({g[0], 0, 0.0}); sres_.depth += 1; sh_levels_.push_back(sh_new_); }
     }
-    if (!*done && g[4]) { sres_.verdict = MC_VERDICT_INVARIANT_VIOLATION; *done = 1; sres_.left_on_queue = g[0]; }
+    if (!*done && g[4]) {
+      sres_.verdict = g[4] == 1 ? MC_VERDICT_ACTION_PROPERTY_VIOLATION : MC_VERDICT_INVARIANT_VIOLATION;
+      *done = 1; sres_.left_on_queue = g[0];
+    }
     if (!*done && sopts_.check_deadlock && g[5]) { sres_.verdict = MC_VERDICT_DEADLOCK; *done = 1; sres_.left_on_queue = g[0]; }
     if (!*done && g[0] == 0) *done = 1;
     if (!*done && sopts_.max_depth && sres_.depth >= sopts_.max_depth) { sres_.verdict = MC_VERDICT_DEPTH_LIMIT; sres_.left_on_queue = g[0]; *done = 1; }
@@ -2795,21 +2847,11 @@ class OrigGpu : public Backend {
     HIPCHK(hipMemset(d_ctr_ + K_EVENT, 0xFF, 8));
     sres_.n_launches += 1;
     if (*done) {
-      sviol_act_.clear();
-      if (sres_.verdict == MC_VERDICT_INVARIANT_VIOLATION && sh_event_ != ~0ull && (sh_event_ & 3) == EV_VIOLATION) {
-        // this rank's violating successor, re-derived from (parent, instance)
-        const u64 key = sh_event_ >> 2, par = key >> 8;
-        const int k = (int)(key & 255);
-        u32 w[NWP];
-        if (hipMemcpy(w, store_.states() + par * NWP, NWP * 4, hipMemcpyDeviceToHost) == hipSuccess) {
-          W s, t; S::unpack(w, s);
-          const int act = successor(s, k, t);
-          sviol_bad_ = SS::violated(t, m_.rt.invariants);
-          sviol_parent_ = ((u64)rank_ << 37) | par; sviol_act_ = act >= 0 ? kOrigActNames[act] : "?";
-          sviol_text_ = state_text(t, true);
-        }
-      }
-      if (sres_.verdict == MC_VERDICT_INVARIANT_VIOLATION) sres_.violated = sviol_act_.empty() ? "" : first_violated(sviol_bad_);
+      // this rank's violating step (shard_level_stats derived it) counts when it is of the kind the
+      // ranks agreed on
+      const bool viol = sres_.verdict == MC_VERDICT_INVARIANT_VIOLATION || sres_.verdict == MC_VERDICT_ACTION_PROPERTY_VIOLATION;
+      if (!viol || sh_event_ == ~0ull || sviol_verdict_ != sres_.verdict) sviol_act_.clear();
+      if (viol) sres_.violated = sviol_act_.empty() ? "" : sviol_name_;
       double secs = 0; for (auto& k : sres_.kernels) secs += k.ms / 1000.0;
       sres_.seconds_kernels = secs;
       finish(sres_, st0_);
@@ -3117,7 +3159,7 @@ class OrigGpu : public Backend {
   u64 sh_level_begin_ = 0, sh_level_count_ = 0, sh_next_write_ = 0, sh_new_ = 0, sh_chunk_begin_ = 0, sh_chunk_count_ = 0;
   u64 seg_off_[8] = {0}, seg_off_ack_[8] = {0}, fill_counts_reply_[8] = {0}, fill_counts_states_[8] = {0};
   u64 fill_counts_route_[8] = {0};
-  u64 sviol_parent_ = 0; u32 sviol_bad_ = 0; std::string sviol_act_, sviol_text_;
+  u64 sviol_parent_ = 0; int sviol_verdict_ = 0; std::string sviol_act_, sviol_text_, sviol_name_;
   u64 sh_event_ = ~0ull;
   std::vector<u64> sh_levels_;   // this rank's states of every level of sres_.levels (the rank file's level rows)
   bool last_fifo_ = true;   // seen-set layout of the last single-GPU run (16-B keyed / 8-B entries)
@@ -3158,6 +3200,21 @@ class OrigGpu : public Backend {
     return act;
   }
 
+  // What a violation event at the step (s, t) of instance k reports: TLC checks the
+  // invariants of a successor it is about to keep (new; or out of the model under MC_COMPAT_INV_OUT_OF_MODEL)
+  // before the implied actions, so a broken invariant is named first; else the first listed property the
+  // step breaks, in cfg order.  (An in-model successor already in the seen-set satisfies every invariant: a
+  // state that breaks one stops the search at the key it was found at, which is smaller.)
+  void name_violation(const W& s, const W& t, int k, bool inv_oom, int& verdict, std::string& name) const {
+    const u32 bad = (S::in_model(t, m_.rt) || inv_oom) ? SS::violated(t, m_.rt.invariants) : 0u;
+    if (bad || !actions()) { verdict = MC_VERDICT_INVARIANT_VIOLATION; name = first_violated(bad); return; }
+    const u32 pbad = S::violated_action(s, t, k, m_.rt.action_props);
+    verdict = MC_VERDICT_ACTION_PROPERTY_VIOLATION;
+    name = "?";
+    for (auto& n : m_.prop_names)
+      if (pbad & orig_prop_bit(n.c_str())) { name = n; break; }
+  }
+
   std::string first_violated(u32 bad) const {
     for (auto& n : m_.inv_names) {
       if (bad & orig_inv_bit(n.c_str())) return n;
@@ -3191,6 +3248,7 @@ class OrigGpu : public Backend {
   X(1, 2, 3, 2, 3)          \
   X(2, 1, 2, 1, 5)          \
   X(2, 1, 2, 1, 6)          \
+  X(2, 1, 2, 1, 7) /* pair7: the smallest model in which commitIndex goes back */ \
   X(2, 1, 3, 2, 5)          \
   X(2, 2, 3, 2, 6)          \
   X(5, 1, 3, 3, 4) /* C5 */ \

@@ -52,7 +52,20 @@ OrigModel resolve_orig_model(const CfgFile& cfg) {
     m.rt.symmetry = 1;
   }
   if (!cfg.action_constraints.empty()) throw CfgError(MC_E_UNSUPPORTED, "ACTION_CONSTRAINTS are not supported for raft_original");
-  if (!cfg.properties.empty()) throw CfgError(MC_E_UNSUPPORTED, "temporal PROPERTIES are not supported");
+  // PROPERTIES: the action properties ([][A]_vars) compiled from configs/raft_original_actions_mc.tla, each
+  // accepted only when the root module, or a module it EXTENDS, states it; nothing else (no liveness)
+  for (size_t k = 0; k < cfg.properties.size(); ++k) {
+    const std::string& n = cfg.properties[k];
+    const u32 bit = orig_prop_bit(n.c_str());
+    if (!bit)
+      throw CfgError(MC_E_UNSUPPORTED, "property '" + n + "': only the [][A]_vars properties of configs/raft_original_actions_mc.tla "
+                                       "are compiled for raft_original (no other temporal PROPERTIES, no liveness)");
+    if (k >= cfg.property_defs.size() || cfg.property_defs[k].empty())
+      throw CfgError(MC_E_UNSUPPORTED, "property '" + n + "': the module and the modules it EXTENDS do not define " + n +
+                                       " (configs/raft_original_actions_mc.tla defines the action properties)");
+    if (!(m.rt.action_props & bit)) m.prop_names.push_back(n);
+    m.rt.action_props |= bit;
+  }
   for (auto& c : cfg.constraints) {
     if (c == "BoundedTerms") m.rt.constraints |= OC_BoundedTerms;
     else if (c == "BoundedLogs") m.rt.constraints |= OC_BoundedLogs;

@@ -106,7 +106,9 @@ __global__ void __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(S::NW <
       ++nsucc;
       atomicAdd(&lds_cnt[act], 1u);
       const bool inm = S::in_model(t, a.rt);
-      if ((inm || a.inv_oom) && evk < 0 && S::violated(t, a.rt.invariants & S::inv_frame(act))) evk = k;
+      if ((inm || a.inv_oom) && evk < 0 &&
+          (action_step_violated<S>(s, t, k, act, a.rt) || S::violated(t, a.rt.invariants & S::inv_frame(act))))
+        evk = k;
       if (inm) {
         ++j;
 #if RMC_SIM_SELECT == 0
@@ -210,7 +212,9 @@ void sim_replay(const OrigRuntime& rt, bool inv_oom, bool deadlock, u64 seed, u6
       for (int q = 0; q < S::AW; ++q) t.allLogs[q] = al[q];
       ++nsucc;
       const bool inm = S::in_model(t, rt);
-      if ((inm || inv_oom) && evk < 0 && S::violated(t, rt.invariants)) { evk = k; ev_act = act; bad = t; }
+      bool viol = S::violated(t, rt.invariants) != 0u;
+      if constexpr (S::ACTIONS) viol = viol || S::violated_action(s, t, k, rt.action_props) != 0u;   // every listed property, unframed
+      if ((inm || inv_oom) && evk < 0 && viol) { evk = k; ev_act = act; bad = t; }
       if (inm && sim_take(key, ++j)) { kept = t; kept_act = act; }
     }
     const u64 len = out.states.size();

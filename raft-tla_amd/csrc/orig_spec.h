@@ -63,6 +63,23 @@ inline u32 orig_inv_bit(const char* n) {
   return 0;
 }
 
+// action properties ([][A]_vars, configs/raft_original_actions_mc.tla; §14 below): OP_* selection bits
+enum { OP_TermsMonotonic = 1, OP_OneVotePerTerm = 2, OP_LeaderAppendOnly = 4, OP_CommittedNeverLost = 8,
+       OP_CommitIndexMonotonic = 16, OP_LeaderNeverStepsDown_false = 32 };
+constexpr int kOrigPropCount = 6;
+static const char* const kOrigPropNames[kOrigPropCount] = {
+    "TermsMonotonic", "OneVotePerTerm", "LeaderAppendOnly", "CommittedNeverLost", "CommitIndexMonotonic",
+    "LeaderNeverStepsDown_false"};
+// OP_* bit of a property name, 0 if it is not one of the compiled ones
+inline u32 orig_prop_bit(const char* n) {
+  for (int k = 0; k < kOrigPropCount; ++k) {
+    const char* a = kOrigPropNames[k]; const char* b = n;
+    while (*a && *a == *b) { ++a; ++b; }
+    if (!*a && !*b) return 1u << k;
+  }
+  return 0;
+}
+
 // error flags raised by the successor function (TLC evaluation errors / capacity)
 enum { OE_EVAL_LOG_INDEX = 1, OE_CAP_ELECTIONS = 2, OE_CAP_COUNT = 4 };
 
@@ -71,6 +88,7 @@ struct OrigRuntime {
   u32 constraints;            // OC_* mask
   u32 invariants;             // OI_* mask (cfg order kept on host)
   u32 symmetry;               // 1 = SYMMETRY Permutations(Server): one seen-set entry per orbit (S::fp_sym)
+  u32 action_props;           // OP_* mask of the cfg's PROPERTIES (cfg order kept on host)
 };
 
 constexpr int perm_count(int n) { return n <= 1 ? 1 : n * perm_count(n - 1); }   // |Permutations(Server)| = N!
@@ -130,6 +148,10 @@ struct Orig {
   static constexpr int I_RECV = LEAD_HI, I_DUP = I_RECV + MK, I_DROP = I_DUP + MK;   // Receive / Duplicate / Drop
   // orig_generate_lead's occupancy hint (waves per SIMD; orig_backend.hip): 4 for states of <= 15 words
   static constexpr int LEAD_WAVES = NW <= 15 ? 4 : 1;
+  // orig_generate's occupancy hint
+  static constexpr int GEN_WAVES = NW <= 15 ? 4 : 1;
+  // action properties are compiled into a kernel through WithActions<S> only (below)
+  static constexpr bool ACTIONS = false;
 
   static_assert(N >= 1 && N <= 7, "N");
   static_assert(N * TB <= 32 && N * VB <= 32 && N * CIB <= 32 && N * N <= 32, "scalar field words");
@@ -886,6 +908,121 @@ struct Orig {
     return m;
   }
 
+  // ---------------------------------------------------------------- §14 action properties ([][A]_vars)
+  // The properties of configs/raft_original_actions_mc.tla on a step (s, t), t = the successor instance
+  // k of apply built from s; returns the OP_* bits of the violated ones among `props`.  A per-server
+  // field is read at a compile-time index (the loops unroll), a log is one word, so
+  //   currentTerm'[i] >= currentTerm[i], commitIndex'[i] >= commitIndex[i]   are field compares of the
+  //                                   term / commit words, skipped altogether when the word is unchanged;
+  //   PrefixOf(log[i], log'[i])       is Len <= Len' and one masked compare of the two log words
+  //                                   (prefix_mask over the first Len(log[i]) entry fields);
+  //   PrefixOf(Committed(i), log'[i]) the same over the first CommittedLen(i) entry fields;
+  //   Restart(i)                      (raft_original.tla:166-174) is the action formula over (s, t), as TLC
+  //                                   evaluates it whatever disjunct of Next built t: every conjunct as a word
+  //                                   compare -- state', commitIndex', votesResponded', votesGranted' are s's
+  //                                   with server i's field Follower / 0 / {} / {}; row i of voterLog',
+  //                                   nextIndex', matchIndex' is the reset row and the other rows are s's;
+  //                                   messages, currentTerm, votedFor, log and elections unchanged.  (k, the
+  //                                   instance, is not consulted: another instance's successor may equal
+  //                                   Restart(i)'s.)  Reached only when some commitIndex field went down.
+  // No runtime-indexed array, no scratch.  Not reached from any kernel but through WithActions<S>.
+  RMC_HD static bool is_restart_step(const Work& s, const Work& t, int i) {
+    u32 st = s.st, ci = s.commit, vr = s.vresp, vg = s.vgrant;
+    fset<2>(st, i, F); fset<CIB>(ci, i, 0u); set_row_bits(vr, i, 0u); set_row_bits(vg, i, 0u);
+    bool same = t.st == st && t.commit == ci && t.vresp == vr && t.vgrant == vg && t.term == s.term && t.voted == s.voted;
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+      same &= t.log.v[j] == s.log.v[j];
+      same &= t.vl.v[j] == (j == i ? (VR)0 : s.vl.v[j]);
+      same &= t.nexti.v[j] == (j == i ? fsplat<NIB, u32>(1, N) : s.nexti.v[j]);
+      same &= t.matchi.v[j] == (j == i ? 0u : s.matchi.v[j]);
+    }
+#pragma unroll
+    for (int q = 0; q < EMAX; ++q) same &= t.el[q] == s.el[q];
+#pragma unroll
+    for (int q = 0; q < MK + 1; ++q) same &= t.bag.v[q] == s.bag.v[q];
+    return same;
+  }
+  RMC_HD static u32 violated_action(const Work& s, const Work& t, int k, u32 props) {
+    (void)k;   // the instance that built t: no property reads it (see Restart(i) above)
+    u32 bad = 0;
+    if ((props & OP_TermsMonotonic) && t.term != s.term) {
+      bool ok = true;
+#pragma unroll
+      for (int i = 0; i < N; ++i) ok &= fget<TB>(t.term, i) >= fget<TB>(s.term, i);
+      if (!ok) bad |= OP_TermsMonotonic;
+    }
+    if ((props & OP_OneVotePerTerm) && t.voted != s.voted) {
+      bool ok = true;
+#pragma unroll
+      for (int i = 0; i < N; ++i) {
+        const u32 v = fget<VB>(s.voted, i);
+        ok &= !(fget<TB>(t.term, i) == fget<TB>(s.term, i) && v != (u32)N) || fget<VB>(t.voted, i) == v;
+      }
+      if (!ok) bad |= OP_OneVotePerTerm;
+    }
+    if (props & OP_LeaderAppendOnly) {
+      bool ok = true;
+#pragma unroll
+      for (int i = 0; i < N; ++i) {
+        const u32 x = s.log.v[i], y = t.log.v[i];
+        const bool pre = llen(x) <= llen(y) && ((x ^ y) & prefix_mask(llen(x))) == 0u;
+        ok &= !(fget<2>(s.st, i) == L && fget<2>(t.st, i) == L) || pre;
+      }
+      if (!ok) bad |= OP_LeaderAppendOnly;
+    }
+    if (props & OP_CommittedNeverLost) {
+      bool ok = true;
+#pragma unroll
+      for (int i = 0; i < N; ++i) {
+        const u32 x = s.log.v[i], y = t.log.v[i];
+        const int ci = g_commit(s, i), n = llen(x), cl = ci <= n ? ci : n;   // CommittedLen(i)
+        ok &= cl <= llen(y) && ((x ^ y) & prefix_mask(cl)) == 0u;
+      }
+      if (!ok) bad |= OP_CommittedNeverLost;
+    }
+    if ((props & OP_CommitIndexMonotonic) && t.commit != s.commit) {
+      bool ok = true;
+#pragma unroll
+      for (int i = 0; i < N; ++i) ok &= fget<CIB>(t.commit, i) >= fget<CIB>(s.commit, i) || is_restart_step(s, t, i);
+      if (!ok) bad |= OP_CommitIndexMonotonic;
+    }
+    if ((props & OP_LeaderNeverStepsDown_false) && t.st != s.st) {   // test-only control
+      bool ok = true;
+#pragma unroll
+      for (int i = 0; i < N; ++i) ok &= fget<2>(s.st, i) != L || fget<2>(t.st, i) == L;
+      if (!ok) bad |= OP_LeaderNeverStepsDown_false;
+    }
+    return bad;
+  }
+
+  // The properties a step of an action can violate: those that read (primed) a variable the action
+  // writes; on the others [A]_vars holds because the variables A reads stutter (writers: inv_frame_safety's
+  // table).  TermsMonotonic reads currentTerm'; OneVotePerTerm votedFor' and currentTerm'; LeaderAppendOnly
+  // log' and state' (state alone can only make its antecedent true: with log' = log the prefix holds, so
+  // the writers of state stay in for a reader's sake and cost one compare); CommittedNeverLost log'
+  // (commitIndex is read unprimed); CommitIndexMonotonic commitIndex' -- Restart writes it too, and its step
+  // satisfies the formula's second disjunct, so it is left out (tests/native/orig_actions_host.cpp checks
+  // that on every reachable Restart step rather than assume it); the control state'.
+  // RequestVote, AppendEntries, DuplicateMessage, DropMessage, DropStaleResponse and the two response
+  // handlers write none of these: their frame is empty.
+  RMC_HD static u32 act_frame(int act) {
+    const bool w_commit = act == OA_AdvanceCommitIndex || act == OA_HandleAppendEntriesRequest;   // but for Restart
+    const bool w_log = act == OA_ClientRequest || act == OA_HandleAppendEntriesRequest;
+    const bool w_state = act == OA_Restart || act == OA_Timeout || act == OA_BecomeLeader || act == OA_UpdateTerm ||
+                         act == OA_HandleAppendEntriesRequest;
+    const bool w_term = act == OA_Timeout || act == OA_UpdateTerm;
+    const bool w_voted = act == OA_Timeout || act == OA_UpdateTerm || act == OA_HandleRequestVoteRequest;
+    u32 m = 0;
+    if (w_term) m |= OP_TermsMonotonic;
+    if (w_term || w_voted) m |= OP_OneVotePerTerm;
+    if (w_log || w_state) m |= OP_LeaderAppendOnly;
+    if (w_log) m |= OP_CommittedNeverLost;
+    if (w_commit) m |= OP_CommitIndexMonotonic;
+    if (w_state) m |= OP_LeaderNeverStepsDown_false;
+    return m;
+  }
+
   // ---------------------------------------------------------------- pack / unpack (canonical stored form)
   RMC_HD static void pack(const Work& t, u32 (&w)[NW]) {
     BitOut<NW> o;
@@ -1229,6 +1366,18 @@ struct WithSafety : B {
   static constexpr int LEAD_WAVES = B::NW <= 15 ? 3 : 1;
   RMC_HD static u32 violated(const Work& t, u32 invs) { return B::violated(t, invs) | B::violated_safety(t, invs); }
   RMC_HD static u32 inv_frame(int act) { return B::inv_frame(act) | B::inv_frame_safety(act); }
+};
+
+// B (S or WithSafety<S>) with the action properties compiled in: a kernel over WithActions<B> evaluates
+// B::violated_action on every step it generates, masked by B::act_frame.  A run whose cfg lists no
+// PROPERTIES launches the kernels over B, whose code holds none of it.
+template <class B>
+struct WithActions : B {
+  static constexpr bool ACTIONS = true;
+  // both states of a step stay live through the check: at 4 waves per SIMD (128 VGPRs) C2's orig_generate
+  // spilled 2 VGPRs (5 over WithSafety) and orig_generate_lead 3; 3 waves (168) hold both without scratch
+  static constexpr int GEN_WAVES = B::NW <= 15 ? 3 : 1;
+  static constexpr int LEAD_WAVES = B::NW <= 15 ? 3 : 1;
 };
 
 }  // namespace rmc

@@ -62,11 +62,13 @@ __global__ void __launch_bounds__(BS) orig_generate_sym(GenArgs a) {
         for (int q = 0; q < S::AW; ++q) t.allLogs[q] = al[q];
         ++nsucc;
         atomicAdd(&lds_cnt[act], 1u);
+        const bool step_bad = action_step_violated<S>(s, t, k, act, a.rt);
         if (S::in_model(t, a.rt)) {
           ++nin;
           fp = S::fp_sym(t, a.seed);
           have = true;
-        } else if (a.inv_oom && S::violated(t, a.rt.invariants & S::inv_frame(act))) {
+          if (step_bad) { const u64 e = ev_word(gid, (u32)k, EV_VIOLATION); ev = e < ev ? e : ev; }
+        } else if (a.inv_oom && (step_bad || S::violated(t, a.rt.invariants & S::inv_frame(act)))) {
           const u64 e = ev_word(gid, (u32)k, EV_VIOLATION);
           ev = e < ev ? e : ev;
         }

@@ -16,11 +16,12 @@ namespace rmc {
 
 struct OrigModel {
   int N = 0, NV = 0, MT = 0, ML = 0, MK = 0;
-  OrigRuntime rt{0, 0, 0, 0, 0};
+  OrigRuntime rt{0, 0, 0, 0, 0, 0};
   std::vector<std::string> server, value;                 // printed names, index order
   std::string follower, candidate, leader, nil, t_rvq, t_rvp, t_aeq, t_aep;
   std::vector<std::string> inv_names;                     // cfg order
   std::vector<std::string> constraint_names;
+  std::vector<std::string> prop_names;                    // PROPERTIES, cfg order
 };
 
 

@@ -393,7 +393,7 @@ def check_loopback(spec, config, world, device_index=0, history_prefixes=None, d
         out = [m.summary() for m in mcs]
         name = next((r.violated for r in out if r.violated), "")
         for m, res in zip(mcs, out):
-            if res.verdict == "INVARIANT_VIOLATION":
+            if res.verdict in ("INVARIANT_VIOLATION", "ACTION_PROPERTY_VIOLATION"):
                 res.violated = name
             if trace:
                 res.trace_text = trace_text(trace, m.action_location)
@@ -482,7 +482,7 @@ class ShardedChecker:
             shard = LibShard(self.mc, self.rank, self.world)
             trace = (fifo_sharded_bfs if self.fifo else sharded_bfs)(shard, self.ex, self.rank, self.device)
         res = self.mc.summary()
-        if res.verdict == "INVARIANT_VIOLATION":   # the name is known on the violating ranks only
+        if res.verdict in ("INVARIANT_VIOLATION", "ACTION_PROPERTY_VIOLATION"):   # the name is known on the violating ranks only
             top = self.ex.allreduce_max(self.world - self.rank if res.violated else 0)
             if top:
                 res.violated = self.ex.broadcast_obj(res.violated, self.world - top)
