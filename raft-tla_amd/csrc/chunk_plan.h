@@ -5,7 +5,9 @@
 // runs in chunks of the whole allocation on one stream (buffer 0 from its start).  A larger level is
 // cut into sub-chunks that alternate between the two halves, so orig_generate of sub-chunk c + 1 can
 // run beside the seen-set probes of sub-chunk c.  Every chunk but a level's last is a whole number
-// of workgroups: records are grouped per generate workgroup.
+// of workgroups: records are grouped per generate workgroup.  A level whose first parents were generated
+// ahead, beside the level before's last dedup (the level hoist), starts with that prefix
+// as its chunk 0, in the half it was generated into.
 #pragma once
 #include <cstdint>
 #include <cstdlib>
@@ -57,9 +59,30 @@ struct ChunkPlan {
 
   bool split(uint64_t level_count) const { return sub != 0 && level_count >= threshold && level_count > sub; }
 
-  // the chunks of a level, in order; returns whether the level is split (pipelined)
-  bool plan(uint64_t level_count, std::vector<Chunk>& out) const {
+  // whether a level's first pre_count parents can have been generated ahead into one half (the level
+  // hoist): whole workgroups unless they are the whole level, and no more than a half
+  bool prefix_ok(uint64_t level_count, uint64_t pre_count) const {
+    return sub != 0 && pre_count <= level_count && pre_count <= half_cap &&
+           (pre_count % (uint64_t)wg == 0 || pre_count == level_count);
+  }
+
+  // the chunks of a level, in order; returns whether the level is split (pipelined).
+  // pre_count > 0: the level's first pre_count parents were generated ahead into half pre_buffer.  They
+  // are chunk 0 as they stand, the rest follows in sub-chunks from the other half on, and the level is
+  // pipelined whatever its size (an unsplit chunk would write over the prefix's records).  A prefix
+  // that is not prefix_ok() gives no plan: out is left empty.
+  bool plan(uint64_t level_count, std::vector<Chunk>& out, uint64_t pre_count = 0, int pre_buffer = 0) const {
     out.clear();
+    if (pre_count) {
+      if (!prefix_ok(level_count, pre_count)) return false;
+      int b = pre_buffer & 1;
+      out.push_back({0, pre_count, b});
+      for (uint64_t first = pre_count; first < level_count; first += sub) {
+        const uint64_t left = level_count - first;
+        out.push_back({first, left < sub ? left : sub, b ^= 1});
+      }
+      return true;
+    }
     const bool sp = split(level_count);
     const uint64_t step = sp ? sub : full_cap;
     int b = 0;

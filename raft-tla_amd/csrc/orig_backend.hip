@@ -1095,6 +1095,21 @@ __global__ void orig_reset_ctr(unsigned long long* ctr) {
   for (int t = threadIdx.x; t < K_NCTR; t += blockDim.x) ctr[t] = t == K_EVENT ? ~0ull : 0ull;
 }
 
+// level start behind a hoisted generate (run()): what orig_generate + orig_generate_lead
+// of the level's first parents counted in their own block goes into the level's counters, and that
+// block is back at orig_reset_ctr's values (its K_LEAD was the hoisted pair's alone).  The counters
+// the generate kernels never touch are zero in ctr2 and stay out.  Vector atomics only, as in
+// orig_advance.
+__global__ void orig_fold_ctr(unsigned long long* ctr, unsigned long long* ctr2) {
+  for (int t = threadIdx.x; t < K_NCTR; t += blockDim.x) {
+    const unsigned long long v = atomicExch(&ctr2[t], t == K_EVENT ? ~0ull : 0ull);
+    if (t == K_EVENT) atomicMin(&ctr[t], v);
+    else if (t == K_ERR) atomicOr(&ctr[t], v);
+    else if (t == K_ERRGID) { if (v) atomicCAS(&ctr[t], 0ull, v); }
+    else if (t == K_GEN_IN || t == K_PROBES || (t >= K_ACT && t < K_ACT + OA_NACT)) atomicAdd(&ctr[t], v);
+  }
+}
+
 // run start: the initial state (global id 0), its meta word (no parent) and its seen-set entry
 // (key 0), written on the run's stream so that nothing at run start blocks the host
 template <int NWP>
@@ -1539,6 +1554,15 @@ class OrigGpu : public Backend {
       HIPCHK(res_.stream(&clear_stream_, hipStreamNonBlocking));
       HIPCHK(res_.event(&clear_ev_, hipEventDisableTiming));
       HIPCHK(res_.event(&gen_ev_, hipEventDisableTiming));
+      // the level hoist (launch_hoist): the hoisted pair's counters, the stream and the events of the
+      // host's look at K_LEVEL_NEW, and the pair's timing events (two pairs: a level reads its own
+      // after the next hoist has been queued)
+      HIPCHK(res_.device(&d_ctr2_, K_NCTR * 8));
+      HIPCHK(res_.pinned(&h_x_, 8));
+      HIPCHK(res_.stream(&x_stream_, hipStreamNonBlocking));
+      HIPCHK(res_.event(&x_ev_, hipEventDisableTiming));
+      HIPCHK(res_.event(&hx_ev_, hipEventDisableTiming));
+      for (int i = 0; i < 4; ++i) HIPCHK(res_.event(&hoist_ev_[i / 2][i % 2]));
       if (2 * slots >= STARTER_FACTOR * STARTER_SLOTS)
         if (int rc = ensure_starter(STARTER_SLOTS, err)) return rc;
     }
@@ -1917,6 +1941,14 @@ class OrigGpu : public Backend {
     int nch = 0;
     u64 nnew = 0;
     double level_ms = 0;
+    // the level hoist (launch_hoist): a level's first `count` parents generated ahead, beside the level
+    // before's last dedup, into half `buffer`, timed by hoist_ev_[slot].  cur: this level's chunk 0;
+    // next: queued for the level after this one (what drain_hoist gives up).  arm: this level's last
+    // dedup leaves room for one
+    struct Hoist { u64 count = 0; int buffer = 0, slot = 0; };
+    Hoist cur, next;
+    bool hoist_on = false, arm = false;
+    u64 hoist_min = 0;
     u64 level_end() const { return level_begin + level_count; }
   };
 
@@ -1950,23 +1982,45 @@ class OrigGpu : public Backend {
     // (the FIFO path is never split)
     s.plan = ChunkPlan(chunk_states_, s.fifo ? 0 : sub_env == ~0ull ? ChunkPlan::default_sub(chunk_states_) : sub_env,
                        env_u64("RAFTMC_OVERLAP_MIN_LEVEL", sub_env == ~0ull ? OVERLAP_MIN_LEVEL : 0), BS);
+    // RAFTMC_HOIST (read per run): 0 = no level hoist (launch_hoist); RAFTMC_HOIST_MIN: the fewest
+    // parents worth generating ahead
+    s.hoist_on = !s.fifo && env_u64("RAFTMC_HOIST", 1) != 0;
+    s.hoist_min = std::max<u64>(BS, env_u64("RAFTMC_HOIST_MIN", OVERLAP_MIN_HALF));
     const u64 S_B = NWP * 4;
+    // an exit from the loop gives up a queued hoist first (drain_hoist)
+    auto leave = [&](int rc) { std::string e2; (void)drain_hoist(s, e2); return rc; };
     while (s.level_count > 0) {
-      if (o.max_depth && r.depth >= o.max_depth) { r.left_on_queue = (int64_t)s.level_count; r.verdict = MC_VERDICT_DEPTH_LIMIT; break; }
+      if (o.max_depth && r.depth >= o.max_depth) {
+        if (int rc = drain_hoist(s, err)) return rc;
+        r.left_on_queue = (int64_t)s.level_count; r.verdict = MC_VERDICT_DEPTH_LIMIT; break;
+      }
       s.last = s.count_last && r.depth + 1 >= o.max_depth;
-      if (int rc = maybe_spill(s, r, err)) return rc;
+      if (int rc = maybe_spill(s, r, err)) return leave(rc);
       if (!ctr_clean_) {
         hipLaunchKernelGGL(orig_reset_ctr, dim3(1), dim3(64), 0, stream_, (unsigned long long*)d_ctr_);
         HIPCHK(hipGetLastError());
       }
       ctr_clean_ = false;
-      if (int rc = maybe_switch_to_full_table(s, r, err)) return rc;
-      if (int rc = queue_level(o, s, r, err)) return rc;
-      if (int rc = read_level(s, r, err)) return rc;
+      if (int rc = maybe_switch_to_full_table(s, r, err)) return leave(rc);
+      s.cur = s.next; s.next = typename Search::Hoist();
+      if (int rc = fold_hoist(s, err)) return rc;
+      // a split level generates the next level's first parents beside its last dedup when that level
+      // will be expanded (this one is not the counted last, max_depth does not stop it) and no
+      // checkpoint is written between the two
+      s.arm = s.hoist_on && !s.last && (s.cur.count || s.plan.split(s.level_count)) &&
+              !(o.max_depth && r.depth + 1 >= o.max_depth) &&
+              !(o.checkpoint_every > 0 && !o.checkpoint_path.empty() && (r.depth + 1) % o.checkpoint_every == 0);
+      if (int rc = queue_level(o, s, r, err)) return leave(rc);
+      if (s.arm)
+        if (int rc = launch_hoist(o, s, r, err)) return leave(rc);
+      if (int rc = read_level(s, r, err)) return leave(rc);
       u64* const c = h_ctr_;
       const u64 level_end = s.level_end(), nnew = s.nnew;
       if (!s.last && level_end + nnew - store_.base() > store_.cap()) c[K_ERR] |= OE_CAP_STORE;
       const bool event = c[K_EVENT] != ~0ull && (c[K_ERR] & ~(u64)OE_CAP_STORE) == 0;
+      // the search stops or starts over here, or the next level is not what the hoist took it for
+      if (event || c[K_ERR] || s.next.count > nnew)
+        if (int rc = drain_hoist(s, err)) return rc;
       if (event && !s.fifo) return research_fifo(o, c[K_EVENT], r, err);
       if (event) {
         // the level's first event in TLC's order stops the search; a full state store only
@@ -1997,9 +2051,12 @@ class OrigGpu : public Backend {
       if (nnew > 0) { r.levels.push_back({(int64_t)nnew, 0, 0.0}); r.depth += 1; }
       s.level_begin += s.level_count;
       s.level_count = nnew;
-      if (o.checkpoint_every > 0 && !o.checkpoint_path.empty() && r.depth % o.checkpoint_every == 0 && s.level_count > 0)
+      if (o.checkpoint_every > 0 && !o.checkpoint_path.empty() && r.depth % o.checkpoint_every == 0 && s.level_count > 0) {
+        if (int rc = drain_hoist(s, err)) return rc;
         if (int rc = save_checkpoint(o.checkpoint_path, r, s.level_begin, s.level_count, err)) return rc;
+      }
     }
+    if (int rc = drain_hoist(s, err)) return rc;
     if (prof_ && prof_acc_[3])
       std::fprintf(stderr, "orig_probe per workgroup (us): %.2f  (%llu workgroups)\n",
                    prof_acc_[1] / 100.0 / prof_acc_[3], (unsigned long long)prof_acc_[3]);
@@ -2042,6 +2099,10 @@ class OrigGpu : public Backend {
     }
     run_table_ = s.tbl; run_mask_ = s.tmask;
     ctr_clean_ = false;
+    // the hoisted pair's counters start every run at orig_reset_ctr's values (clear_stream_, where a
+    // run that returned early would have left a hoisted generate, is idle: waited for above)
+    hipLaunchKernelGGL(orig_reset_ctr, dim3(1), dim3(64), 0, stream_, (unsigned long long*)d_ctr2_);
+    HIPCHK(hipGetLastError());
     return 0;
   }
 
@@ -2075,11 +2136,13 @@ class OrigGpu : public Backend {
   // The device keeps what the search still reads (the frontier) and writes (the next level);
   // when the next level, predicted from the last growth ratio with a 1.5x margin, might not fit
   // behind what is stored, the completed levels move to host memory.
-  int maybe_spill(const Search& s, const RunResult& r, std::string& err) {
+  int maybe_spill(Search& s, const RunResult& r, std::string& err) {
     if (s.level_begin <= store_.base() || s.last) return 0;
     const double prev = r.levels.size() >= 2 ? (double)r.levels[r.levels.size() - 2].states : 1.0;
     const double pred = (double)s.level_count * std::max(1.0, (double)s.level_count / std::max(prev, 1.0)) * 1.5;
     if ((double)(store_.total() - store_.base()) + pred <= (double)store_.cap()) return 0;
+    // a hoisted generate reads the store by device index: it is given up before anything moves
+    if (int rc = drain_hoist(s, err)) return rc;
     if (progress_) std::fprintf(stderr, "spilling %llu completed states to host memory\n", (unsigned long long)(s.level_begin - store_.base()));
     return store_.spill(s.level_begin, s.level_count, stream_, progress_, err);
   }
@@ -2128,9 +2191,15 @@ class OrigGpu : public Backend {
   //                                   re-armed on the generate stream itself, behind lead(c + 1)
   //   counter readback             <- stream_ order: the last materialize, which waited for the
   //                                   last generate, which is behind every earlier one
+  // Behind a level hoist (launch_hoist, s.cur) chunk 0 has its records already: no generate is queued
+  // for it, its dedup waits for the hoisted lead's event, and the gen_ev_ edge (orig_reset_ctr,
+  // orig_fold_ctr, orig_migrate) is chunk 1's, the level's first generate into d_ctr_.
   int queue_level(const RunOpts& o, Search& s, RunResult& r, std::string& err) {
-    s.ovl = s.plan.plan(s.level_count, chunks_);
+    s.ovl = s.plan.plan(s.level_count, chunks_, s.cur.count, s.cur.buffer);
     const int nchunks = (int)chunks_.size();
+    if (s.cur.count && !nchunks) { err = "level hoist: the generated prefix does not fit the level"; return MC_E_STATE; }
+    if (!s.ovl || nchunks < 2) s.arm = false;
+    const int first_gen = s.cur.count ? 1 : 0;   // chunk 0 of a level behind a hoist has its records already
     hipStream_t const gst = s.ovl ? clear_stream_ : stream_;
     for (s.nch = 0; s.nch < nchunks; ++s.nch) {
       const int q = s.nch;
@@ -2142,29 +2211,34 @@ class OrigGpu : public Backend {
       if (!e[7]) { err = "hipEventCreate failed"; return MC_E_NO_DEVICE; }
       // kernels index the device store (global id - store_.base()); keys and parent pointers are global
       const GenArgs g = gen_args(cb - store_.base(), cnt, cb, r.seed, o, rec0);
-      if (s.ovl && q == 0) {
-        HIPCHK(hipEventRecord(gen_ev_, stream_));
-        HIPCHK(hipStreamWaitEvent(gst, gen_ev_, 0));
-      }
-      if (s.ovl && q >= 2) HIPCHK(hipStreamWaitEvent(gst, pool_ev(8 * (q - 2) + 3), 0));
-      HIPCHK(hipEventRecord(e[0], gst));
-      launch_generate(g, nblk, gst);
-      HIPCHK(hipGetLastError());
-      HIPCHK(hipEventRecord(e[1], gst));
-      if (s.ovl) {
+      hipEvent_t gen_done = e[1];
+      // (gen_ev_ before anything of the level is on stream_: behind a hoist, chunk 1's generate runs
+      // beside chunk 0's dedup)
+      if (s.ovl && q == 0) HIPCHK(hipEventRecord(gen_ev_, stream_));
+      if (q < first_gen) {
+        gen_done = hoist_ev_[s.cur.slot][1];
+      } else {
+        if (s.ovl && q == first_gen) HIPCHK(hipStreamWaitEvent(gst, gen_ev_, 0));
+        if (s.ovl && q >= 2) HIPCHK(hipStreamWaitEvent(gst, pool_ev(8 * (q - 2) + 3), 0));
+        HIPCHK(hipEventRecord(e[0], gst));
+        launch_generate(g, nblk, gst);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(e[1], gst));
         // K_LEAD for the next sub-chunk's generate, in order behind this one's lead kernel (not
         // after the level's last: orig_reset_ctr does that, and a late zeroing here could hit the
         // next level's count)
-        if (q + 1 < nchunks) HIPCHK(hipMemsetAsync(d_ctr_ + K_LEAD, 0, 8, gst));
-        HIPCHK(hipStreamWaitEvent(stream_, e[1], 0));
+        if (s.ovl && q + 1 < nchunks) HIPCHK(hipMemsetAsync(d_ctr_ + K_LEAD, 0, 8, gst));
+      }
+      if (s.ovl) {
+        HIPCHK(hipStreamWaitEvent(stream_, gen_done, 0));
         HIPCHK(hipEventRecord(e[2], stream_));   // dedup's own start: e[1] is the other stream's
       }
       // the seen-set pass, then the store pass: each one sequence per search order.  Beside a generate
-      // (every pipelined sub-chunk but the level's last) the -workers N probes run at 4 workgroups per
+      // (every pipelined sub-chunk but the level's last, and that one before a hoist) the -workers N probes run at 4 workgroups per
       // CU, not 8, with 2 probes in flight per thread, not 4: see launch_dedup_plain
       const DedupArgs d = dedup_args(g, cb, s.tbl, s.tmask);
       if (s.fifo) { if (int rc = queue_merge_probe(s, d, nblk, err)) return rc; }
-      else launch_dedup_plain(d, nblk, s.ovl && q + 1 < nchunks, s.count_probes);
+      else launch_dedup_plain(d, nblk, s.ovl && (q + 1 < nchunks || s.arm), s.count_probes);
       HIPCHK(hipGetLastError());
       HIPCHK(hipEventRecord(e[3], stream_));
       if (s.fifo) { if (int rc = queue_winners_materialize(s, cb, cnt, nblk, e[5], err)) return rc; }
@@ -2176,10 +2250,78 @@ class OrigGpu : public Backend {
       if (q + 1 < nchunks) {
         hipLaunchKernelGGL(orig_advance, dim3(1), dim3(64), 0, stream_, (unsigned long long*)d_ctr_, s.ovl ? 0 : 1);
         HIPCHK(hipGetLastError());
+        // K_LEVEL_NEW is final from here on: what launch_hoist reads
+        if (s.arm && q + 2 == nchunks) HIPCHK(hipEventRecord(x_ev_, stream_));
       }
       for (size_t k = 0; k < r.kernels.size(); ++k) if (s.fifo || k != 2) r.kernels[k].launches += 1;
       r.kernels[0].algo_bytes += (double)cnt * NWP * 4;        // + G_in * 10 record bytes per level (read_level)
     }
+    return 0;
+  }
+
+  // The level hoist: the next level's first generate beside this level's last dedup.
+  // orig_generate touches neither the seen-set nor the level's counters' meaning: it needs its
+  // parents in the store and a free half of the record buffers, and both are there before the level
+  // ends.  With the whole level queued (s.arm: queue_level launched the last dedup in its
+  // beside-generate form and recorded x_ev_ behind orig_advance of sub-chunk k - 2) the host reads
+  // K_LEVEL_NEW as that kernel left it: X new states of sub-chunks 0 .. k - 2 are stored from
+  // level_end on and nothing changes the word again.  The 8-byte copy runs on a stream of its own, so
+  // it queues behind neither dedup(k - 1) nor generate(k - 1); the device has all the level's work
+  // already.  Then, on the generate stream:
+  //   hoisted generate  <- e[7] of k - 2: its states are stored, its half's records have been read
+  //                        (stream order: behind generate(k - 1), the half's other user is k - 2)
+  // over parents [level_end, level_end + X0) into the half sub-chunk k - 1 does not use, counting into
+  // d_ctr2_, so this level's readback sees nothing of the next level (fold_hoist adds the block in
+  // at the next level's start), timed by events of its own (the pool's belong to this level).  Every
+  // kernel argument is the host's; a hoist under s.hoist_min parents is not worth its launch.
+  int launch_hoist(const RunOpts& o, Search& s, RunResult& r, std::string& err) {
+    const int k = (int)chunks_.size();
+    HIPCHK(hipStreamWaitEvent(x_stream_, x_ev_, 0));
+    HIPCHK(hipMemcpyAsync(h_x_, d_ctr_ + K_LEVEL_NEW, 8, hipMemcpyDeviceToHost, x_stream_));
+    HIPCHK(hipEventRecord(hx_ev_, x_stream_));
+    HIPCHK(hipEventSynchronize(hx_ev_));
+    // whole workgroups, one half at the most, and only slots the store has (a full store ends the
+    // search at this level's readback)
+    const u64 dev0 = s.level_end() - store_.base();
+    const u64 room = store_.cap() > dev0 ? store_.cap() - dev0 : 0;
+    const u64 x0 = std::min<u64>(std::min<u64>(*h_x_, room), s.plan.half_cap) / BS * BS;
+    if (x0 < s.hoist_min) return 0;
+    typename Search::Hoist h;
+    h.count = x0; h.buffer = chunks_[k - 1].buffer ^ 1; h.slot = s.cur.slot ^ 1;
+    GenArgs g = gen_args(dev0, x0, s.level_end(), r.seed, o, h.buffer ? s.plan.half_cap : 0);
+    g.ctr = (unsigned long long*)d_ctr2_;
+    HIPCHK(hipStreamWaitEvent(clear_stream_, pool_ev(8 * (k - 2) + 7), 0));
+    HIPCHK(hipEventRecord(hoist_ev_[h.slot][0], clear_stream_));
+    launch_generate(g, (unsigned)(x0 / BS), clear_stream_);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(hoist_ev_[h.slot][1], clear_stream_));
+    s.next = h;
+    if (progress_)
+      std::fprintf(stderr, "level hoist: %llu parents of level %lld generated beside the last dedup of level %lld\n",
+                   (unsigned long long)x0, (long long)r.depth + 1, (long long)r.depth);
+    return 0;
+  }
+
+  // level start behind a hoist (s.cur): the hoisted pair's counters into the level's, behind
+  // orig_reset_ctr (stream order) and the pair itself
+  int fold_hoist(const Search& s, std::string& err) {
+    if (!s.cur.count) return 0;
+    HIPCHK(hipStreamWaitEvent(stream_, hoist_ev_[s.cur.slot][1], 0));
+    hipLaunchKernelGGL(orig_fold_ctr, dim3(1), dim3(64), 0, stream_, (unsigned long long*)d_ctr_, (unsigned long long*)d_ctr2_);
+    HIPCHK(hipGetLastError());
+    return 0;
+  }
+
+  // Every way out of the level loop but the next level's queue_level comes through here first: a
+  // queued hoist (s.next) is waited for and forgotten, its counters are reset, and the generate stream
+  // and both halves are free for whatever follows (a FIFO re-search, a spill, a checkpoint, the next
+  // run of the handle).
+  int drain_hoist(Search& s, std::string& err) {
+    if (!s.next.count) return 0;
+    s.next = typename Search::Hoist();
+    HIPCHK(hipStreamSynchronize(clear_stream_));
+    hipLaunchKernelGGL(orig_reset_ctr, dim3(1), dim3(64), 0, stream_, (unsigned long long*)d_ctr2_);
+    HIPCHK(hipGetLastError());
     return 0;
   }
 
@@ -2236,7 +2378,9 @@ class OrigGpu : public Backend {
       const std::pair<int, int> pr[4] = {{0, 1}, {s.ovl ? 2 : 1, 3}, {3, fifo ? 5 : 3}, {fifo ? 5 : 3, 7}};
       for (int k = 0; k < 4; ++k) {
         float ms = 0;
-        if (pr[k].first != pr[k].second) (void)hipEventElapsedTime(&ms, pool_ev(8 * q + pr[k].first), pool_ev(8 * q + pr[k].second));
+        // (chunk 0 behind a hoist: its generate ran in the level before, timed by the hoist's own pair)
+        if (k == 0 && q == 0 && s.cur.count) (void)hipEventElapsedTime(&ms, hoist_ev_[s.cur.slot][0], hoist_ev_[s.cur.slot][1]);
+        else if (pr[k].first != pr[k].second) (void)hipEventElapsedTime(&ms, pool_ev(8 * q + pr[k].first), pool_ev(8 * q + pr[k].second));
         r.kernels[k].ms += ms; level_ms += ms;
       }
     }
@@ -3146,6 +3290,10 @@ class OrigGpu : public Backend {
   u64* d_starter_ = nullptr; u64 starter_cap_ = 0;
   hipStream_t clear_stream_ = nullptr; hipEvent_t clear_ev_ = nullptr;
   hipEvent_t gen_ev_ = nullptr;          // pipelined level: stream_ is ready for the level's first generate
+  // the level hoist (launch_hoist)
+  u64* d_ctr2_ = nullptr; u64* h_x_ = nullptr;
+  hipStream_t x_stream_ = nullptr;
+  hipEvent_t x_ev_ = nullptr, hx_ev_ = nullptr, hoist_ev_[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
   std::vector<Chunk> chunks_;            // the current level's chunks (chunk_plan.h)
   u64* run_table_ = nullptr; u64 run_mask_ = 0;   // the table the last single-GPU run ended on (entries - 1)
   u64 table_mask_ = 0, chunk_states_ = 0;
@@ -3181,6 +3329,7 @@ class OrigGpu : public Backend {
   void release() {
     // a run that returned early may have left the full table's clear in flight
     if (clear_stream_) (void)hipStreamSynchronize(clear_stream_);
+    if (x_stream_) (void)hipStreamSynchronize(x_stream_);
     if (stream_) (void)hipStreamSynchronize(stream_);
     res_.release();   // streams last
     store_.release();
